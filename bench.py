@@ -8,7 +8,15 @@ resident in HBM.  Weak scaling: every rank processes B_local=4 frame pairs; valu
 processed by all ranks / max-over-ranks wall time of exactly K steps (barrier + device sync on both
 sides).  Multi-GPU: one process per GPU (torchrun), gradients exchanged with RCCL all_reduce.
 
-Also reported (same JSON line):
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+headline line (metric, value, unit, ms_per_step, dtype, math, step_roofline, final_losses).
+`--dump-outputs DIR` also writes what the last timed step left with its caller (see dump_outputs); so
+that two such runs can be compared value for value, a run with it computes the warp input gradients
+on the ordered, atomic-free route (ops.set_deterministic) instead of the default atomic scatter, and
+says so in the line's `warp_backward`.  Runs without it time the default kernels.
+Everything below takes runs of its own, or hooks into the timed ones, and is measured only with `--full`.
+
+With --full also reported (same JSON line):
   math          the conv arithmetic of the headline: bf16x6 (fp32-equivalent split products) in
                 every forward, data-gradient and weight-gradient conv (--math / VST_CONV_MATH).
   roofline      the dominant conv launch of the step by time, out of roofline_convs: the ResnetBlock
@@ -32,6 +40,7 @@ Also reported (same JSON line):
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -633,6 +642,42 @@ def cpu_baseline_and_parity(init_sd, batch_cpu, hip_losses0, steps=2):
     return base, parity
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20   # all of --dump-outputs' files together (float32), headers aside
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each tensor of `arrays` (name -> tensor) as path/<name>.npy, float32
+    (float64 kept).  The budget is shared evenly: an array with more elements than its share is
+    written as a fixed sample of them, flat, at sorted indices drawn once from numpy's
+    default_rng(DUMP_SAMPLE_SEED + position), so two builds given the same arguments write the same
+    elements.  Weights, batch and image-pool draws are seeded, and a run that writes its outputs takes
+    the warp input gradients' ordered route (ops.set_deterministic; main), so runs of one build with the
+    same arguments write the same values.  (On the default atomic scatter the summation order changes
+    from run to run and Adam amplifies it: parameters 7e-4 and images 0.09 apart after 3 steps, images
+    O(1) apart after 25.)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))   # bytes per array
+    total = 0
+    for i, (name, t) in enumerate(arrays.items()):
+        t = t.detach()
+        a = np.ascontiguousarray((t if t.dtype == torch.float64 else t.float()).cpu().numpy())
+        cap = share // a.itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED + i).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 * 10 ** 6, total
+    return total
+
+
+def _flat_params(net):
+    """Every parameter of a network after the last update, flat, in state_dict order."""
+    return torch.cat([v.detach().reshape(-1).float() for v in net.state_dict().values()])
+
+
 def time_steps(model, steps, hook_g, hook_d, world, device):
     return time_fn(lambda: model.optimize_parameters(hook_g, hook_d), steps, world, device)
 
@@ -684,7 +729,8 @@ def _line(metric, value, unit, world, args, ms, config, math):
     return {"metric": metric, "value": round(value, 3), "unit": unit, "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "fp32" if math in ("bf16x6", "fp32") else math,
-            "math": {"policy": math, "conv": MATH_LABEL[math]}, "data": "synthetic (random-init weights)",
+            "math": {"policy": math, "conv": MATH_LABEL[math]}, "warp_backward": args.warp_backward,
+            "data": "synthetic (random-init weights)",
             "config": config}
 
 
@@ -704,7 +750,15 @@ def workload_c4(args, world, rank, local, device):
     lo, lt = torch.randint(0, 4, (B,), generator=g), torch.randint(0, 4, (B,), generator=g)
     for _ in range(max(5, args.warmup)):
         sol.train_step(x, lo, lt)
-    el = time_fn(lambda: sol.train_step(x, lo, lt), args.steps, world, device)
+    last = {}
+
+    def step():
+        last["loss"] = sol.train_step(x, lo, lt)
+    el = time_fn(step, args.steps, world, device)
+    if args.dump_outputs and rank == 0:
+        arrays = {"loss_" + k.replace("/", "_"): v.reshape(1) for k, v in last.get("loss", {}).items()}
+        arrays.update(params_G=_flat_params(sol.G), params_D=_flat_params(sol.D))
+        dump_outputs(args.dump_outputs, arrays)
     cfg = {"workload": "C4: StarGAN solver iteration (D step + WGAN-GP every iteration, G step every 5th), "
                        "%dx%d, c_dim 4, conv_dim 64, 6+6 repeats, B_local=%d" % (args.size, args.size, B),
            "global_batch": B * world, "height": args.size, "width": args.size, "parallelism": "dp%d" % world,
@@ -733,6 +787,8 @@ def workload_c5(args, world, rank, local, device):
     for _ in range(max(2, args.warmup + args.warmup % 2)):   # even: the timed steps start at an E-step
         m.optimize_parameters(ex, ex, ex)
     el = time_fn(lambda: m.optimize_parameters(ex, ex, ex), args.steps, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, _model_outputs(m))
     cfg = {"workload": "C5: MoGAN optimize_parameters (E/M alternating, 8 RAFT flows x 20 iterations), "
                        "ngf=ndf=64, %dx%d, B_local=%d, pool_size=%d" % (W, H, B, args.pool),
            "global_batch": B * world, "height": H, "width": W, "parallelism": "dp%d" % world,
@@ -740,6 +796,18 @@ def workload_c5(args, world, rank, local, device):
            if world > 1 else None}
     return _line("frames/sec: MoGAN train step (RAFT flow) 1024x436", B * world * args.steps / el, "frames/s", world,
                  args, el / args.steps * 1e3, cfg, args.math)
+
+
+def _model_outputs(model):
+    """What a caller of optimize_parameters() has afterwards: the step's losses (loss_names order,
+    float64), its visuals (NCHW) and every network's parameters."""
+    arrays = {"losses": torch.tensor(list(model.get_current_losses().values()), dtype=torch.float64)}
+    for k, v in model.get_current_visuals().items():
+        if torch.is_tensor(v):
+            arrays["visual_" + k] = v
+    for k in model.model_names:
+        arrays["params_" + k] = _flat_params(getattr(model, "net" + k))
+    return arrays
 
 
 def free_port():
@@ -794,8 +862,15 @@ def main():
     ap.add_argument("--pool", type=int, default=50)
     ap.add_argument("--math", default=os.environ.get("VST_CONV_MATH", "bf16x6"),
                     help="conv arithmetic policy of the headline (fp32-equivalent bf16x6 by default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (c2): the conv rooflines probed inside the "
+                         "timed steps, inference, the mixed policy, the extras, the CPU baselines and parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (losses, visuals, network "
+                         "parameters; large arrays as a fixed seeded sample) as DIR/<name>.npy; such a run takes "
+                         "the deterministic warp-backward route so that its outputs repeat")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the rooflines and the extras")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = {"c2": 4, "c4": 4, "c5": 1, "dpcheck": 1}[args.workload]
@@ -827,6 +902,14 @@ def main():
 
     ops.set_conv_math(args.math)
     torch.manual_seed(0)
+    random.seed(0)   # the image pools draw from Python's global generator
+    # a run whose outputs are written is a run to be compared with another: its warp input gradients take the
+    # ordered, atomic-free route, so that with the seeds above it computes the same steps every time.  Every
+    # other run times the default atomic scatter kernels; the result line names the route ("warp_backward")
+    prev_det = ops.set_deterministic(True)
+    if not args.dump_outputs:
+        ops.set_deterministic(prev_det)
+    args.warp_backward = "ordered, atomic-free" if (args.dump_outputs or prev_det) else "atomic scatter (default)"
     if args.workload != "c2":
         out = {"c4": workload_c4, "c5": workload_c5}[args.workload](args, world, rank, local, device)
         if rank == 0:
@@ -843,7 +926,10 @@ def main():
         dp.broadcast_params(list(nets.values()))
         ex = dp.GradExchange(world).attach(list(nets.values()))
         hookG = hookD = ex
-    init_sd = {k: {n: t.detach().cpu().clone() for n, t in v.state_dict().items()} for k, v in nets.items()}
+    cpu_leg = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    extras = args.full and rank == 0 and not args.no_extras
+    if cpu_leg:
+        init_sd = {k: {n: t.detach().cpu().clone() for n, t in v.state_dict().items()} for k, v in nets.items()}
     B, S = args.batch, args.size
     batch_cpu = synthetic_batch(B, S, S, seed=1234 + rank, device="cpu")
     a, a2, b, mask, flow = [t.to(device) for t in batch_cpu]
@@ -853,16 +939,21 @@ def main():
     losses0 = None
     for i in range(max(1, args.warmup)):
         model.optimize_parameters(hookG, hookD)
-        if i == 0:
+        if i == 0 and cpu_leg:
             losses0 = model.get_current_losses()  # step 0: what the parity leg checks
-    # one launch in 13 of each probed op timed (36 per step each): HIP event pairs idle the stream between kernels
-    probes = {k: ops.LaunchProbe(v, every=PROBE_EVERY) for k, v in DOMINANT_KEYS(B).items()}
-    ops.set_launch_probes(list(probes.values()))
+    probes = {}
+    if args.full:
+        # one launch in 13 of each probed op timed (36 per step each): HIP event pairs idle the stream between kernels
+        probes = {k: ops.LaunchProbe(v, every=PROBE_EVERY) for k, v in DOMINANT_KEYS(B).items()}
+        ops.set_launch_probes(list(probes.values()))
     elapsed = time_steps(model, args.steps, hookG, hookD, world, device)
     ops.set_launch_probes([])
     for p in probes.values():
         p.steps = args.steps
     losses = model.get_current_losses()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, _model_outputs(model))
+    ops.set_deterministic(prev_det)   # --full's other legs run the routes they always run
 
     frames = B * world * args.steps
     value = frames / elapsed
@@ -874,6 +965,7 @@ def main():
         "dtype": "fp32" if args.math in ("bf16x6", "fp32") else args.math,
         "math": {"policy": args.math, "conv": MATH_LABEL[args.math],
                  "elementwise_and_reductions": "fp32 / fp64 (IN statistics, losses, bias sums)"},
+        "warp_backward": args.warp_backward,
         "data": "synthetic (SURVEY §8d generator; random-init weights, init_type=normal 0.02)",
         "config": {"workload": "C2: CycleGANCon optimize_parameters, resnet_9blocks G + basic PatchGAN D, "
                                "ngf=ndf=64, %dx%d, B_local=%d, pool_size=%d, flow-warp temporal loss" % (S, S, B, args.pool),
@@ -884,7 +976,7 @@ def main():
                                         "whole train step per GPU: 2.1753 TFLOP/frame of conv work (SURVEY §8d)"),
         "final_losses": {k: round(v, 5) for k, v in losses.items()},
     }
-    if rank == 0 and not args.no_extras:
+    if extras:
         rl = {k: conv_roofline(k, p, args.math) for k, p in probes.items()}
         # the dominant kernel of the step is conv_fprop_bf_k<256x128> (its forward AND stride-1
         # data-gradient launches); its roofline line is the forward launch (one kernel, whole CU
@@ -892,7 +984,7 @@ def main():
         # roofline_convs
         out["roofline"] = rl["resblock_fprop"] or next(v for v in rl.values() if v)
         out["roofline_convs"] = rl
-    if rank == 0 and world == 1 and not args.no_extras:
+    if extras and world == 1:
         G_inf = _g_inference_model(device)
         out["inference"] = _isolated(inference_fps, device, G=G_inf)
         # the same step under the round-1 "mixed" policy, separately labelled (not the headline)
@@ -916,7 +1008,7 @@ def main():
                          "mogan_train": _isolated(mogan_train_fps, device)}
         if not args.no_cpu_baseline:
             out["inference"]["cpu_baseline"] = inference_cpu_baseline(device, G=G_inf)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if cpu_leg:
         out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(init_sd, batch_cpu, losses0)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -9,7 +9,7 @@
 # steps:
 #   tests[=PYTEST_ARGS]  the GPU suite (default: tests -m gpu), or the given files / -k filter
 #   smoke                __graft_entry__.smoke()
-#   bench[=BENCH_ARGS]   bench.py's JSON line -> bench.json (default: the driver's default run)
+#   bench[=BENCH_ARGS]   bench.py's JSON line -> bench.json (default: --full, the whole record)
 #   trace                C2 step kernel trace -> trace/step_summary.txt            (tools/gpu_trace.sh)
 #   inftrace             inference kernel traces B=1 / B=16 / 436x1024 -> inf/     (tools/gpu_inftrace.sh)
 #   layertable           per-conv-op table of one C2 step -> layertable.jsonl       (tools/layertable.py)
@@ -42,7 +42,7 @@ for step in "$@"; do
       timeout -k 10 300 python3 -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1
       rc=$?; tail -2 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python3 bench.py $arg > $O/bench.json 2> $O/bench.err
+      timeout -k 10 600 python3 bench.py ${arg:---full} > $O/bench.json 2> $O/bench.err
       rc=$?; tail -c 600 $O/bench.json; [ $rc -ne 0 ] && tail -20 $O/bench.err ;;
     trace)
       TAG=$TAG/trace bash tools/gpu_trace.sh; rc=$? ;;
