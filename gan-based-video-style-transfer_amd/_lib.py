@@ -116,6 +116,10 @@ SIGNATURES = {
     "vst_warp_masked_bwd_input": (I, [P, P, P, I, I, I, I, I, P]),
     "vst_warp_bwd_det_ws_bytes": (SZ, [I, I, I]),
     "vst_warp_bwd_input_det": (I, [P, P, P, P, SZ, I, I, I, I, I, I, I, I, P]),
+    "vst_temporal_sqdiff_part_floats": (I, [I, I, I, I]),
+    "vst_temporal_sqdiff_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, P]),
+    "vst_temporal_sqdiff_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, P]),
+    "vst_resize_bilinear": (I, [P, P, P, I, I, I, I, I, I, P]),
     "vst_instnorm_affine_fwd": (I, [P, P, P, P, P, F, P, P, I, I, I, I, F, P]),
     "vst_instnorm_affine_ws_bytes": (SZ, [I, I, I]),
     "vst_instnorm_affine_bwd": (I, [P, P, P, P, P, P, F, P, P, P, P, P, P, I, I, I, I, F, I, P]),

@@ -20,7 +20,7 @@ Only ``n_styles == 1`` (plain InstanceNorm2d(affine=True)) is on the HIP path; t
 import torch
 import torch.nn as nn
 
-from . import ops, perceptual
+from . import fs_lib, ops, perceptual
 from .networks import Conv2d, FlatNet, _Marker, _ToNCHW, _ToNHWC, _pad_channels, _padded_bias
 from .ops import cpad
 from .optim import FusedAdam
@@ -399,6 +399,101 @@ class Johnson:
         """fs_johnson.py:50-52: styled frame / 255."""
         _, styled = self.model(frame.to(self.device).float())
         return styled / 255.0
+
+
+class _VideoFastStyle(Johnson):
+    """The frame-pair train step Huang and ReCoNet share (fs_huang.py:28-67, fs_reconet.py:28-78) on
+    Johnson's plumbing (FusedAdam, prep_adam, style-Gram cache, VGG handle, infer_method).
+
+    Both frames run as ONE batch of 2B (frames 1, then frames 2) through FastStyleNet and the VGG:
+    InstanceNorm, the Grams and every loss mean are per sample, so the arithmetic is the two separate
+    passes' and the GEMMs see twice the rows.  With it
+      content = (alpha/2) (mse_1 + mse_2) = alpha * mse over the 2B batch,
+      style   = (beta/2) sum_levels (mse(G_1) + mse(G_2)) = beta * sum_levels mse over the 2B Grams,
+    and the temporal terms are the fused masked-warp loss (fs_lib.temporal_loss_pair_nhwc)."""
+
+    def _pair_features(self, x):
+        """x: [2B,H,W,4] in [0,1] -> (feature map, styled 0..255, content loss, style loss)."""
+        feats, styled = self.model.forward_nhwc(x)
+        with torch.no_grad():
+            xc = perceptual.normalize_nhwc(x)
+        styled_f, img_f = self.vgg.forward_multi_nhwc([perceptual.normalize_nhwc(styled, d0=255.0), xc],
+                                                      [len(self.vgg.slices_idx), 3])
+        content = perceptual.mse_loss(styled_f[2], img_f[2], self.alpha)
+        style = None
+        for f, gs in zip(styled_f, self._style_targets(x.shape[0])):
+            t = perceptual.mse_loss(perceptual.gram_nhwc(f), gs, self.beta)
+            style = t if style is None else style + t
+        return feats, styled, content, style
+
+    def train_step(self, imgs, masks, flows):
+        """imgs: list of [B,3,H,W] frames in [0,1] (the first two are used); masks [B,k,H,W]; flows
+        [B,2k,H,W] (pair 0: masks[:, 0:1], flows[:, 0:2]).  prep_adam + train_method + adam.step;
+        returns the losses in the reference's order (device scalars) and styled frame 2 (NHWC4, 0..255)."""
+        self.prep_adam(self.itr)
+        dev = self.device
+        x = ops.nchw_to_nhwc(torch.cat([imgs[0].to(dev).float(), imgs[1].to(dev).float()]).contiguous())
+        B = imgs[0].shape[0]
+        flow = flows[:, 0:2].to(dev).float().contiguous()
+        mask = masks[:, 0:1].to(dev).float().contiguous()
+        out = self.losses_nhwc(x, flow, mask)
+        out[0].backward()
+        self.adam.step()
+        self.itr += 1
+        return tuple(v.detach() for v in out[:-1]), out[-1][B:]
+
+
+class Huang(_VideoFastStyle):
+    """fs_huang.py:8-71: Johnson's perceptual losses on two consecutive frames + the output temporal
+    loss gamma * mean((mask * (styled2 - warp(styled1, flow)))^2); TV on styled frame 1 only.
+    emphasis = (alpha, beta, gamma, delta); train_step returns ((total, content, style, temporal, tv),
+    styled frame 2)."""
+
+    def __init__(self, style_imgs, emphasis=(1.0, 1e5, 1e2, 1e-6), lr=1e-3, batch_sz=16, device="cuda",
+                 vgg=None, model=None):
+        alpha, beta, self.gamma, delta = emphasis
+        super().__init__(style_imgs, (alpha, beta, delta), lr, batch_sz, device, vgg, model)
+
+    def losses_nhwc(self, x, flow, mask):
+        """train_method's loss graph on the NHWC4 [0,1] frames x ([2B,H,W,4]: frames 1, then frames 2), flow
+        [B,2,H,W], mask [B,1,H,W] -> (loss, content, style, temporal, tv, styled [2B,H,W,4] 0..255)."""
+        B = x.shape[0] // 2
+        _, styled, content, style = self._pair_features(x)
+        temporal = fs_lib.temporal_loss_pair_nhwc(styled, flow, mask, self.gamma, ab_scale=1.0 / 255.0, cl=3)
+        # calc_tv_loss(styled1 / 255) == calc_tv_loss(styled1) / 255 (positively homogeneous)
+        tv = perceptual.tv_loss_nhwc(styled[:B], self.delta / 255.0, 3)
+        loss = content + style + temporal + tv
+        return loss, content, style, temporal, tv, styled
+
+
+class Reconet(_VideoFastStyle):
+    """fs_reconet.py:8-82: the perceptual losses on two consecutive frames + the feature-map temporal
+    loss at the residual blocks' output (flow and mask resized to it) + the output temporal loss with
+    the luminance-weighted input term; TV averaged over both styled frames.
+    emphasis = (alpha, beta, gamma_f, gamma_o, delta); train_step returns ((total, content, style,
+    f_temporal, o_temporal, tv), styled frame 2)."""
+
+    def __init__(self, style_imgs, emphasis=(1.0, 1e5, 1e2, 1e2, 1e-6), lr=1e-3, batch_sz=16, device="cuda",
+                 vgg=None, model=None):
+        alpha, beta, self.gamma_f, self.gamma_o, delta = emphasis
+        super().__init__(style_imgs, (alpha, beta, delta), lr, batch_sz, device, vgg, model)
+
+    def losses_nhwc(self, x, flow, mask):
+        """As Huang.losses_nhwc -> (loss, content, style, f_temporal, o_temporal, tv, styled)."""
+        B, H, W = x.shape[0] // 2, x.shape[1], x.shape[2]
+        feats, styled, content, style = self._pair_features(x)
+        Hf, Wf = feats.shape[1], feats.shape[2]
+        # fs_reconet.py:58-59 scales flow channel 0 (x) by the HEIGHT ratio and channel 1 (y) by the WIDTH ratio;
+        # passed as the reference computes them (at every size the net takes, H and W multiples of 4, both are 1/4)
+        fflow = ops.resize_bilinear(flow, (Hf, Wf), (float(Hf) / H, float(Wf) / W))
+        fmask = ops.resize_bilinear(mask, (Hf, Wf))
+        f_temporal = fs_lib.temporal_loss_pair_nhwc(feats, fflow, fmask, self.gamma_f)
+        o_temporal = fs_lib.temporal_loss_pair_nhwc(styled, flow, mask, self.gamma_o, inputs=(x[:B], x[B:]),
+                                                    ab_scale=1.0 / 255.0, cl=3)
+        # (delta/2) (tv_1 + tv_2): the TV sum over the 2B batch
+        tv = perceptual.tv_loss_nhwc(styled, self.delta / 2.0 / 255.0, 3)
+        loss = content + style + f_temporal + o_temporal + tv
+        return loss, content, style, f_temporal, o_temporal, tv, styled
 
 
 from . import _lib as _lib_routes  # noqa: E402

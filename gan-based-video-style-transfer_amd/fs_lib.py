@@ -33,3 +33,60 @@ def warp(x, flo):
     """fs_lib.py:5-39 on NCHW x [B,C,H,W] and flow [B,2,H,W] (pixels, channel 0 = x)."""
     C = x.shape[1]
     return _nhwc_to_nchw(warp_nhwc(_nchw_to_nhwc(x), flo), C)
+
+
+class _TemporalLossNHWC(torch.autograd.Function):
+    """The users of ``warp`` in the reference (fs_huang.py:55-56, fs_reconet.py:61-69) as one fused
+    node: warp, validity, mask, optional input term, squared mean (ops.temporal_sqdiff).  ``pair``:
+    a and b are the two halves of one batch tensor ``ab`` ([2B,...]: frames 1 then frames 2, the way the
+    video trainers run the net), so the backward fills one gradient tensor and no slice node copies."""
+
+    @staticmethod
+    def forward(ctx, a, b, flow, mask, scale, ab_scale, cl, i1, i2, pair):
+        ctx.save_for_backward(a, b, flow, mask, i1, i2)
+        ctx.conf = (scale, ab_scale, cl, pair)
+        if pair:
+            a, b = a[:a.shape[0] // 2], a[a.shape[0] // 2:]
+        return ops.temporal_sqdiff(a, b, flow, mask, scale, cl, ab_scale, None if i1 is None else (i1, i2))
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, flow, mask, i1, i2 = ctx.saved_tensors
+        scale, ab_scale, cl, pair = ctx.conf
+        need_a, need_b = (True, True) if pair else ctx.needs_input_grad[:2]
+        if pair:
+            B = a.shape[0] // 2
+            gab = torch.empty_like(a)
+            a, b = a[:B], a[B:]
+            ga, gb = gab[:B].zero_(), gab[B:]
+        else:
+            ga = torch.zeros_like(a) if need_a else None
+            gb = torch.empty_like(b) if need_b else None
+        if need_a or need_b:
+            ops.temporal_sqdiff_bwd(a, b, flow, mask, g.contiguous(), ga, gb, scale, cl, ab_scale,
+                                    None if i1 is None else (i1, i2))
+        return ((gab, None) if pair else (ga, gb)) + (None,) * 8
+
+
+def _temporal_args(flow, mask, inputs):
+    i1, i2 = (None, None) if inputs is None else (inputs[0].detach().contiguous(), inputs[1].detach().contiguous())
+    return flow.detach().contiguous().float(), mask.detach().contiguous().float(), i1, i2
+
+
+def temporal_loss_nhwc(a, b, flow, mask, scale, inputs=None, ab_scale=1.0, cl=None):
+    """scale * mean((mask * (s*b - warp(s*a, flow) - r))^2) as a device scalar, differentiable in a and b.
+    a, b: [B,H,W,Cs] (cl logical channels, default Cs); flow [B,2,H,W]; mask [B,1,H,W]; s = ab_scale.
+    inputs = (i1, i2), NHWC4 input frames: r = the luminance-weighted input term of fs_reconet.py:66-67
+    (a, b then are NHWC4 images, cl = 3); no gradient flows into flow, mask or the inputs."""
+    flow, mask, i1, i2 = _temporal_args(flow, mask, inputs)
+    return _TemporalLossNHWC.apply(a.contiguous(), b.contiguous(), flow, mask, float(scale), float(ab_scale), cl,
+                                   i1, i2, False)
+
+
+def temporal_loss_pair_nhwc(ab, flow, mask, scale, inputs=None, ab_scale=1.0, cl=None):
+    """temporal_loss_nhwc(ab[:B], ab[B:], ...) for the frame pairs stacked as one [2B,H,W,Cs] batch."""
+    if ab.shape[0] % 2:
+        raise ValueError("temporal_loss_pair_nhwc: the batch holds frame pairs (even size), got %d" % ab.shape[0])
+    flow, mask, i1, i2 = _temporal_args(flow, mask, inputs)
+    return _TemporalLossNHWC.apply(ab.contiguous(), None, flow, mask, float(scale), float(ab_scale), cl, i1, i2,
+                                   True)

@@ -15,6 +15,9 @@ library's NHWC layout on the device.  Backward passes are themselves ``vst::`` o
   vst::warp_bilinear(x, flow)                  utils/flowtools.py:18-32 (F.grid_sample, zeros)
   vst::fbcheck(flow_fw, flow_bw)               utils/flowtools.py:34-58 (fbcCheckTorch)
   vst::temporal_loss(a, b, flow, mask, lam)    CycleGANCon cycle_gan_model.py:191-204
+  vst::temporal_sqdiff(a, b, flow, mask, scale, ab_scale, i1?, i2?)   learning-based fs_huang.py:55-56,
+        fs_reconet.py:61-69 (fs_lib.warp validity, optional luminance input term)
+  vst::resize_bilinear(x, out_h, out_w, mult?) F.interpolate(mode='bilinear'), fs_reconet.py:57-60
   vst::gram(f)                                 learning-based fast_style_transfer.py:813-817
   vst::adam_(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step)   torch.optim.Adam step
 
@@ -336,6 +339,66 @@ def _tl_bwd(ctx, grad):
 temporal_loss.register_autograd(_tl_bwd, setup_context=_tl_setup)
 
 
+@torch.library.custom_op("vst::temporal_sqdiff", mutates_args=())
+def temporal_sqdiff(a: Tensor, b: Tensor, flow: Tensor, mask: Tensor, scale: float, ab_scale: float,
+                    i1: Optional[Tensor], i2: Optional[Tensor]) -> Tensor:
+    """scale * mean((mask * (s*b - fs_lib.warp(s*a, flow) - r))^2) over [B,C,H,W] a, b (C = 3 or a multiple
+    of 4), s = ab_scale (fs_huang.py:55-56, fs_reconet.py:61-69).  i1, i2 (both or neither; [B,3,H,W] input
+    frames, a and b then 3-channel images): r = 0.2126 d0 + 0.7152 d1 + 0.0722 d2, d = i2 - warp(i1, flow)."""
+    C = a.shape[1]
+    inputs = None if i1 is None else (_nhwc(i1), _nhwc(i2))
+    return ops.temporal_sqdiff(_nhwc(a), _nhwc(b), flow.contiguous(), mask.contiguous(), scale, C, ab_scale, inputs)
+
+
+@temporal_sqdiff.register_fake
+def _(a, b, flow, mask, scale, ab_scale, i1, i2):
+    return a.new_empty(())
+
+
+@torch.library.custom_op("vst::temporal_sqdiff_backward", mutates_args=())
+def temporal_sqdiff_backward(grad: Tensor, a: Tensor, b: Tensor, flow: Tensor, mask: Tensor, scale: float,
+                             ab_scale: float, i1: Optional[Tensor], i2: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    C = a.shape[1]
+    an, bn = _nhwc(a), _nhwc(b)
+    inputs = None if i1 is None else (_nhwc(i1), _nhwc(i2))
+    ga, gb = torch.zeros_like(an), torch.empty_like(bn)
+    ops.temporal_sqdiff_bwd(an, bn, flow.contiguous(), mask.contiguous(), grad.contiguous(), ga, gb, scale, C,
+                            ab_scale, inputs)
+    return ops.nhwc_to_nchw(ga, C), ops.nhwc_to_nchw(gb, C)
+
+
+@temporal_sqdiff_backward.register_fake
+def _(grad, a, b, flow, mask, scale, ab_scale, i1, i2):
+    return torch.empty_like(a), torch.empty_like(b)
+
+
+def _tsq_setup(ctx, inputs, output):
+    a, b, flow, mask, scale, ab_scale, i1, i2 = inputs
+    ctx.save_for_backward(a, b, flow, mask, i1, i2)
+    ctx.conf = (scale, ab_scale)
+
+
+def _tsq_bwd(ctx, grad):
+    a, b, flow, mask, i1, i2 = ctx.saved_tensors
+    ga, gb = torch.ops.vst.temporal_sqdiff_backward(grad, a, b, flow, mask, *ctx.conf, i1, i2)
+    return ga, gb, None, None, None, None, None, None
+
+
+temporal_sqdiff.register_autograd(_tsq_bwd, setup_context=_tsq_setup)
+
+
+@torch.library.custom_op("vst::resize_bilinear", mutates_args=())
+def resize_bilinear(x: Tensor, out_h: int, out_w: int, mult: Optional[List[float]]) -> Tensor:
+    """F.interpolate(x, size=(out_h, out_w), mode='bilinear', align_corners=False) of [B,C,H,W] planes, channel c
+    times mult[c] (fs_reconet.py:57-60: the flow and mask at feature-map resolution)."""
+    return ops.resize_bilinear(x.contiguous(), (out_h, out_w), mult)
+
+
+@resize_bilinear.register_fake
+def _(x, out_h, out_w, mult):
+    return x.new_empty((x.shape[0], x.shape[1], out_h, out_w))
+
+
 @torch.library.custom_op("vst::gram", mutates_args=())
 def gram(f: Tensor) -> Tensor:
     """fast_style_transfer.py:813-817 gram_matrix of [B,C,H,W] features: bmm(F, F^T) / (h*w) per
@@ -390,4 +453,5 @@ def _(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
 
 OPS: List[str] = ["conv2d", "conv2d_backward", "conv_transpose2d", "conv_transpose2d_backward",
                   "instance_norm_act", "instance_norm_act_backward", "warp_bilinear", "warp_bilinear_backward",
-                  "fbcheck", "temporal_loss", "temporal_loss_backward", "gram", "gram_backward", "adam_"]
+                  "fbcheck", "temporal_loss", "temporal_loss_backward", "temporal_sqdiff", "temporal_sqdiff_backward",
+                  "resize_bilinear", "gram", "gram_backward", "adam_"]

@@ -821,6 +821,68 @@ def warp_masked_bwd_nhwc(gout, flow, align_corners=False):
     return gx
 
 
+def _tsq_args(a, b, flow, mask, cl, inputs):
+    N, H, W, Cs = a.shape
+    i1, i2 = inputs if inputs is not None else (None, None)
+    _dev_check(a, b, flow, mask, i1, i2)
+    if b.shape != a.shape or flow.shape != (N, 2, H, W) or mask.numel() != N * H * W:
+        raise ValueError("temporal_sqdiff: a/b %s %s, flow %s, mask %s do not match" %
+                         (tuple(a.shape), tuple(b.shape), tuple(flow.shape), tuple(mask.shape)))
+    if inputs is not None and (i1.shape != (N, H, W, 4) or i2.shape != (N, H, W, 4)):
+        raise ValueError("temporal_sqdiff: the input frames must be NHWC4 of the frames' size")
+    return N, H, W, Cs, (Cs if cl is None else cl), i1, i2
+
+
+def temporal_sqdiff(a, b, flow, mask, scale, cl=None, ab_scale=1.0, inputs=None):
+    """scale * mean((mask * (s*b - fs_lib.warp(s*a, flow) - r))^2) over the cl logical channels of NHWC a, b
+    (fs_huang.py:55-56, fs_reconet.py:61-69); s = ab_scale; inputs = (i1, i2) NHWC4 frames: r = their
+    luminance-weighted warped difference (fs_reconet.py:66-67), else 0.  One fused pass; device scalar."""
+    N, H, W, Cs, cl, i1, i2 = _tsq_args(a, b, flow, mask, cl, inputs)
+    loss = torch.empty((), device=a.device)
+    part = torch.empty(lib().vst_temporal_sqdiff_part_floats(N, H, W, Cs), device=a.device)
+    _call("vst_temporal_sqdiff_fwd", _p(a), _p(b), _p(flow), _p(mask), _p(i1), _p(i2), _p(loss), _p(part),
+          N, H, W, Cs, cl, float(scale), float(ab_scale), _stream())
+    return loss
+
+
+def temporal_sqdiff_bwd(a, b, flow, mask, gout, ga, gb, scale, cl=None, ab_scale=1.0, inputs=None):
+    """Gradients of temporal_sqdiff: gb written (pad channels 0), ga ACCUMULATED (zero it first); either may
+    be None.  Deterministic mode: gb first, then ga from the ordered scatter of -gb through valid samples."""
+    N, H, W, Cs, cl, i1, i2 = _tsq_args(a, b, flow, mask, cl, inputs)
+    _dev_check(gout, ga, gb)
+    args = (N, H, W, Cs, cl, float(scale), float(ab_scale), _stream())
+    if _deterministic and ga is not None:
+        gbuf = gb if gb is not None else torch.empty_like(a)
+        _call("vst_temporal_sqdiff_bwd", _p(a), _p(b), _p(flow), _p(mask), _p(i1), _p(i2), _p(gout), None,
+              _p(gbuf), *args)
+        _warp_bwd_det(gbuf, flow, ga, False, True, True, cl)
+        return
+    _call("vst_temporal_sqdiff_bwd", _p(a), _p(b), _p(flow), _p(mask), _p(i1), _p(i2), _p(gout), _p(ga), _p(gb),
+          *args)
+
+
+_MULT_CACHE = {}
+
+
+def resize_bilinear(x, size, mult=None):
+    """F.interpolate(x, size=size, mode='bilinear', align_corners=False) of NCHW planes, channel c times
+    mult[c] (a sequence of C floats or None): the flow / mask resize of fs_reconet.py:57-60."""
+    _dev_check(x)
+    N, C, Hi, Wi = x.shape
+    Ho, Wo = int(size[0]), int(size[1])
+    m = None
+    if mult is not None:
+        key = (tuple(float(v) for v in mult), str(x.device))
+        if len(key[0]) != C:
+            raise ValueError("resize_bilinear: one multiplier per channel")
+        if key not in _MULT_CACHE:
+            _MULT_CACHE[key] = torch.tensor(key[0], device=x.device, dtype=torch.float32)
+        m = _MULT_CACHE[key]
+    y = torch.empty((N, C, Ho, Wo), device=x.device, dtype=torch.float32)
+    _call("vst_resize_bilinear", _p(x), _p(m), _p(y), N, C, Hi, Wi, Ho, Wo, _stream())
+    return y
+
+
 def instnorm_affine_fwd(y, stats, gamma, beta, act="none", gate=None, gate_mult=1.0, residual=None,
                         slope=0.0):
     """s * act(gamma * IN(y) + beta) + residual (vst_instnorm_affine_fwd); gamma/beta padded to C."""

@@ -28,6 +28,8 @@
  *                               (cycle_gan_model.py:94-95), temporal loss cycle_gan_model.py:204
  *   vst_adam_step               torch.optim.Adam as constructed at cycle_gan_model.py:97-98
  *   vst_warp_masked_*           methods/learning-based/fs_lib.py:5-39 warp (grid_sample * validity mask)
+ *   vst_temporal_sqdiff_*       methods/learning-based/fs_huang.py:55-56, fs_reconet.py:61-69 temporal losses
+ *   vst_resize_bilinear         F.interpolate(mode='bilinear') of the flow / mask planes, fs_reconet.py:57-60
  *   vst_instnorm_affine_*       nn.InstanceNorm2d(affine=True) (+ReLU, + ResidualBlock layer_strength
  *                               gate) of methods/learning-based/network.py:147-298 (FastStyleNet)
  *   vst_upsample2x_*            F.interpolate(scale_factor=2) in network.py:206-207
@@ -432,6 +434,27 @@ int vst_warp_masked_fwd(const float* x, const float* flow, float* out, int N, in
                         int align_corners, void* stream);
 int vst_warp_masked_bwd_input(const float* gout, const float* flow, float* gx, int N, int H, int W,
                               int Cs, int align_corners, void* stream);
+/* Temporal losses of the video methods (fs_huang.py:55-56, fs_reconet.py:61-69), one fused pass each way:
+ *   loss = scale * mean_{c < Cl}((mask * (s*b - warp_m(s*a, flow) - r))^2),  s = ab_scale,
+ * warp_m = fs_lib.warp (vst_warp_masked_fwd).  a, b: NHWC (C stride Cs, Cl > Cs - 4 logical channels);
+ * flow [N][2][H][W]; mask [N][H][W] (any float, not assumed binary).  i1 = i2 = NULL: r = 0.  Both given
+ * (NHWC4 input frames; a, b then Cs = 4, Cl = 3): r = 0.2126 d0 + 0.7152 d1 + 0.0722 d2 with
+ * d = i2 - warp_m(i1, flow) (fs_reconet.py:66-67), no gradient.  part: vst_temporal_sqdiff_part_floats
+ * floats (fp64 per-block partials, fixed-order finish: the loss is bit-reproducible).
+ * bwd: gb WRITTEN (channels >= Cl zero); ga ACCUMULATED by fp32 atomics through valid samples — either may be
+ * NULL (the deterministic route: gb, then vst_warp_bwd_input_det(gb, masked = 1, negate = 1)).  No gradient
+ * flows to flow, mask, i1, i2. */
+int vst_temporal_sqdiff_part_floats(int N, int H, int W, int Cs);
+int vst_temporal_sqdiff_fwd(const float* a, const float* b, const float* flow, const float* mask,
+                            const float* i1, const float* i2, float* loss, float* part, int N, int H, int W,
+                            int Cs, int Cl, float scale, float ab_scale, void* stream);
+int vst_temporal_sqdiff_bwd(const float* a, const float* b, const float* flow, const float* mask,
+                            const float* i1, const float* i2, const float* gout, float* ga, float* gb, int N,
+                            int H, int W, int Cs, int Cl, float scale, float ab_scale, void* stream);
+/* F.interpolate(x, size=(Ho, Wo), mode='bilinear', align_corners=False) of NCHW planes (no antialias, any
+ * sizes), times mult[c] (device, C floats; NULL = 1): the flow / mask resize of fs_reconet.py:57-60. */
+int vst_resize_bilinear(const float* x, const float* mult, float* y, int N, int C, int Hi, int Wi, int Ho,
+                        int Wo, void* stream);
 /* Affine instance norm: y = s * act(gamma[c] * xhat + beta[c]) + residual, with stats from
  * vst_instnorm_stats; s = 1 (gate NULL) or s = 2|u|/(1+|u|), u = gate_mult * gate[0] (device scalar:
  * ResidualBlock layer_strength, network.py:241-245).  residual may be NULL.  C = 4*2^k <= 1024. */
