@@ -223,14 +223,19 @@ FILE_FLAGS = {"conv_bf.hip": ["-fno-slp-vectorize"]}
 def apply_route_overrides(module_name, g):
     """Developer A/B of the mirror's route selectors (module attributes the tests flip in-process): the one
     environment variable VST_ROUTES="ops.WGRAD_NHWC=0,networks.TAP_H=0" sets them at import (tools/ab_step.sh
-    arms).  Unknown names raise, so a stale arm cannot silently measure the default."""
+    arms).  Unknown modules and names and an item without a value raise, so a stale or misspelled arm cannot
+    silently measure the default."""
     spec = os.environ.get("VST_ROUTES", "").strip()
     if not spec:
         return
     short = module_name.rsplit(".", 1)[-1]
     for item in spec.split(","):
-        name, _, val = item.strip().partition("=")
+        name, eq, val = item.strip().partition("=")
         mod, _, flag = name.partition(".")
+        if not eq:
+            raise ValueError("VST_ROUTES: %r is not module.FLAG=value" % item.strip())
+        if mod not in ("ops", "networks"):
+            raise ValueError("VST_ROUTES: %r names neither ops nor networks" % item.strip())
         if mod != short:
             continue
         if flag not in g:

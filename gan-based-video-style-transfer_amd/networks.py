@@ -490,14 +490,11 @@ class ResnetGenerator(FlatNet):
         return _GeneratorFn.apply(x, self._anchor(), self)
 
 
-# The IN backward writes the weight gradient's dy operand image itself (bf16 planes,
-# ops.instnorm_act_bwd(planes=True)) when that weight gradient runs on the x6 split-bf16 kernel;
-# False keeps the separate plane copy inside vst_conv2d_wgrad.
-IN_PLANES = True
-# The forward IN apply writes the padded channel-major image of its output that the x6 weight
-# gradient of the consuming conv reads (ops.instnorm_act_fwd(cp=...)); False makes that copy
-# inside vst_conv2d_wgrad instead.
-IN_XT = True
+# Which operand images the IN passes write for a conv's weight gradient is decided in one place, _wgrad_form,
+# from the weight gradient's route; these two switches only say whether the producers write the images of an
+# ops.WG_IMAGES route (False: vst_conv2d_wgrad_pre makes its copies itself).
+IN_PLANES = True  # the IN backward writes dy's channel-major bf16 planes
+IN_XT = True      # the forward IN apply writes x's padded channel-major image
 # The IN backward partials of the layer below taken by the ResnetBlock data gradient's own GEMM epilogue and
 # border add (ops.conv2d_dgrad_refl_in: no partial pass reading g and the IN input again).
 # C2 step A/B, same box: 53.52-53.57 vs 53.79-53.80 ms (profiles/r05h_dgrad_epi_step_ab.jsonl); False
@@ -516,37 +513,46 @@ D0_TFWD = True
 # 53.99-54.05 ms (profiles/r05n_apre_bwd_step_ab.jsonl).  (The forward half — planes written beside the fp32
 # activation — measured +0.73 ms in round 5, profiles/r05l_apre_step_ab.jsonl, and was deleted in round 6.)
 APRE_BWD = True
-_WPLAN_BF = 2  # ops.WPLAN_NAMES: copies + conv_wgrad_bf_k
 
 
-@functools.lru_cache(maxsize=256)
-def _wgrad_on_bf(N, H, W, Cx, Ho, Wo, Cyp, R, st, policy):
-    return ops.conv_plan_wgrad(N, H, W, Cx, Ho, Wo, Cyp, R, R, st, "bwd")[0] == _WPLAN_BF
+def _rb_chain(N, H, W, C):
+    """Is the ResnetBlock chain (3x3, reflect pad 1, C -> C at H x W) the planes-only chain (APRE_BWD)?  Only where
+    every one of its data gradients takes the epilogue route (ops.conv2d_dgrad_refl_in), which reads the planes;
+    the other data-gradient routes read the fp32 image."""
+    return APRE_BWD and DGRAD_EPI and C % 8 == 0 and ops.dgrad_refl_epi_ok(N, H, W, C, C)
+
+
+def _wgrad_form(x_shape, y_shape, R, st, train_w, chain=False):
+    """What the producers of a conv's weight-gradient operands write, from its route (ops.wgrad_route) alone:
+    (x_t: the forward IN apply writes x's padded channel-major image, planes: the IN backward writes dy's
+    channel-major bf16 planes, apre: it writes dy as its NHWC bf16 planes ONLY).  The conv reads x_shape and writes
+    y_shape (R x R, stride st, padding (R - 1) // 2); chain: it sits in the planes-only ResnetBlock chain.
+        WG_NHWC (False, False, True)    WG_IMAGES (IN_XT, IN_PLANES, chain and IN_PLANES)    others: nothing
+    dy is planes-only only when every reader takes planes: the epilogue data gradient (chain) and a weight gradient
+    on WG_NHWC, or on WG_IMAGES with the channel-major planes.  Where the weight gradient needs fp32, dy is fp32
+    and the next data gradient reads that (Data layout)."""
+    if train_w:
+        N, H, W, Cx = x_shape
+        _, Ho, Wo, Cyp = y_shape
+        route = ops.wgrad_route(N, H, W, Cx, Ho, Wo, Cyp, R, R, st, (R - 1) // 2, dy_nhwc_planes=chain)
+        if route == ops.WG_NHWC:
+            return False, False, True
+        if route == ops.WG_IMAGES:
+            return IN_XT, IN_PLANES, chain and IN_PLANES
+    return False, False, False
 
 
 def _rb_wgrad_nhwc(N, H, W, C):
-    """Do the ResnetBlock convs (3x3, stride 1, reflect pad 1, C -> C at H x W) take their weight gradients on the
-    NHWC operands (ops.conv2d_wgrad(dy_apl=...)): x = the conv's own NHWC input, dy = the NHWC planes the
-    planes-only backward chain (APRE_BWD) writes?  Then the IN passes write neither the padded channel-major
-    x image nor dy's channel-major planes."""
-    return (APRE_BWD and DGRAD_EPI and ops.dgrad_refl_epi_ok(N, H, W, C, C) and
-            ops.wgrad_nhwc_ok(N, H, W, C, H, W, C, 3, 1, 1, ops.get_conv_math()))
+    """Do the ResnetBlock convs take their weight gradients on ops.WG_NHWC, dy from the planes-only chain?"""
+    return _rb_chain(N, H, W, C) and _wgrad_form((N, H, W, C), (N, H, W, C), 3, 1, True, True) == (False, False, True)
 
 
-def _in_bwd_for_wgrad(g, y, s, act, slope, db, x_in, R, st, want, apre=False):
-    """instnorm_act_bwd -> (dy, dy_planes or None); planes only when the wgrad of the conv below
-    (input x_in, kernel R, stride st) takes the x6 split-bf16 path (apre: dy's NHWC planes too; with the
-    NHWC-operand weight gradient those alone, dy_planes None)."""
-    if want and IN_PLANES:
-        N, H, W, Cx = x_in.shape
-        _, Ho, Wo, Cyp = y.shape
-        if apre and ops.wgrad_nhwc_ok(N, H, W, Cx, Ho, Wo, Cyp, R, st, (R - 1) // 2, ops.get_conv_math()):
-            return ops.instnorm_act_bwd(g, y, s, act, slope, db=db, apre=True), None
-        if not apre and ops.wgrad_nhwc_f32_ok(N, H, W, Cx, Ho, Wo, Cyp, R, st, (R - 1) // 2):
-            return ops.instnorm_act_bwd(g, y, s, act, slope, db=db), None  # the wgrad reads dy's fp32 itself
-        if _wgrad_on_bf(N, H, W, Cx, Ho, Wo, Cyp, R, st, ops.get_conv_math()):
-            return ops.instnorm_act_bwd(g, y, s, act, slope, db=db, planes=True, apre=apre)
-    return ops.instnorm_act_bwd(g, y, s, act, slope, db=db), None
+def _in_bwd_for_wgrad(g, y, s, act, slope, db, x_in, R, st, train_w, chain=False):
+    """instnorm_act_bwd -> (dy, dy_planes or None), dy in the form the weight gradient of the conv below
+    (input x_in, kernel R, stride st) reads (_wgrad_form)."""
+    _, planes, apre = _wgrad_form(x_in.shape, y.shape, R, st, train_w, chain)
+    r = ops.instnorm_act_bwd(g, y, s, act, slope, db=db, planes=planes, apre=apre)
+    return r if planes else (r, None)
 
 
 class _GeneratorFn(torch.autograd.Function):
@@ -563,19 +569,19 @@ class _GeneratorFn(torch.autograd.Function):
 
         train_w = role == "fwd" and anchor.requires_grad
 
+        # the ResnetBlock convs' (two stride-2 convs below the input) planes-only chain, decided here for the backward too
+        rb = (N, ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1, cpad(4 * ngf))
+        sv["chain"] = chain = bool(train_w and blocks and _rb_chain(*rb) and all(
+            P["ikf"].get(f"b{i}{c}") is not None for i in range(len(blocks)) for c in "ab"))
+
         def cp_for(y, cout, st, mode):
-            """(pad, mode, stride) of the 3x3 conv consuming act(IN(y)) (cout outputs) when its x6
-            weight gradient will read the padded channel-major image the IN apply can write."""
-            if not (train_w and IN_XT):
-                return None
-            N_, H_, W_, C_ = y.shape
-            if st == 1 and mode == "reflect" and cout == C_ and _rb_wgrad_nhwc(N_, H_, W_, C_):
-                return None  # a ResnetBlock conv: its weight gradient reads y's NHWC activation itself
-            Ho_, Wo_ = (H_ + 2 - 3) // st + 1, (W_ + 2 - 3) // st + 1
-            if st == 2 and ops.wgrad_nhwc_f32_ok(N_, H_, W_, C_, Ho_, Wo_, cpad(cout), 3, 2, 1):
-                return None  # a stride-2 conv whose weight gradient reads the NHWC operands (fp32 dy)
-            return (1, mode, st) if _wgrad_on_bf(N_, H_, W_, C_, Ho_, Wo_, cpad(cout), 3, st,
-                                                 ops.get_conv_math()) else None
+            """(pad, mode, stride) of the 3x3 conv consuming act(IN(y)) (cout outputs) when its weight
+            gradient will read the padded channel-major image the IN apply can write (_wgrad_form)."""
+            N_, H_, W_, _ = y.shape
+            out_shape = (N_, (H_ + 2 - 3) // st + 1, (W_ + 2 - 3) // st + 1, cpad(cout))
+            # the stride-1 convs are the ResnetBlocks'
+            x_t, _, _ = _wgrad_form(y.shape, out_shape, 3, st, train_w, chain=st == 1 and chain)
+            return (1, mode, st) if x_t else None
 
         def in_act(y, s, act, cp, residual=None):
             if cp is None:
@@ -638,12 +644,12 @@ class _GeneratorFn(torch.autograd.Function):
                 sv["ftap_sw"] = ops.tap_conv_wgrad_swap_ok(y, 7, 3, "reflect", co=net.output_nc)
                 sv["ftap_h"] = not sv["ftap_sw"] and TAP_HW and ops.tap_conv_wgrad_h_ok(y, 7, 3, "reflect")
             if i == 1 and "ftap" in P and train_w and IN_XT:
-                N_, H_, W_, C_ = y.shape
+                # each tap weight gradient is a GEMM of its own reshaped problem: x's image in that geometry
                 if sv["ftap_sw"]:
-                    cp = ("planes", (3, "reflect", ops.tap_swap_geom(W_, 7)[0]))
+                    cp = ("planes", (3, "reflect", ops.tap_swap_geom(y.shape[2], 7)[0]))
                 elif sv["ftap_h"]:
                     cp = (4, "reflect", 1)
-                elif _wgrad_on_bf(N_, H_, W_, C_, H_, W_, 4 * 49, 1, 1, ops.get_conv_math()):
+                elif ops.tap_conv_wgrad_bf_ok(y, 7):
                     cp = (0, "zero", 1)
             an, at = in_act(y, s, "relu", cp)
             sv["xt"][id(an)] = at
@@ -685,14 +691,14 @@ class _GeneratorFn(torch.autograd.Function):
                              R, R, st, pad, mode, co, ci, ci * R * R, R * R, accumulate=True, dy_planes=dy_planes,
                              x_t=xts.get(id(inp)))
 
-        def in_bwd(g, y, s, act, mod, x_in=None, R=3, st=1, apre=False):
+        def in_bwd(g, y, s, act, mod, x_in=None, R=3, st=1, chain=False):
             # IN(+act) backward; the bias gradient of the conv feeding the IN comes out of the
-            # same reduction (sum of dy per channel).  x_in given: also the dy planes of that
-            # conv's x6 weight gradient (None when it runs elsewhere) -> (dy, planes)
+            # same reduction (sum of dy per channel).  x_in given: dy in the form that conv's weight
+            # gradient reads (_wgrad_form) -> (dy, planes or None)
             db = mod.bias.grad if (train_w and mod.bias is not None) else None
             if x_in is None:
                 return ops.instnorm_act_bwd(g, y, s, act, db=db)
-            return _in_bwd_for_wgrad(g, y, s, act, 0.0, db, x_in, R, st, train_w, apre=apre)
+            return _in_bwd_for_wgrad(g, y, s, act, 0.0, db, x_in, R, st, train_w, chain=chain)
 
         def dgrad_reflect(dy, key, cin_p, R, p, H, W, addend=None):
             ikf = P["ikf"].get(key)
@@ -751,36 +757,25 @@ class _GeneratorFn(torch.autograd.Function):
             done(m)
             kc, _, _ = P[f"u{i}"]
             ga = ops.conv2d_fwd(dy, kc, None, a_in.shape[-1], 3, 3, 2, 1, "zero", role="bwd")
-        def dgrad_reflect_in(dy, key, H, W, y_in, s_in, act, mod, x_w, R_w, st_w, addend=None, apre=False):
+        def dgrad_reflect_in(dy, key, H, W, y_in, s_in, act, mod, x_w, R_w, st_w, addend=None, chain=False):
             """dgrad_reflect (3x3, pad 1) + the IN(+act) backward of the layer below it (y_in, s_in;
             mod = the conv feeding that IN; x_w / R_w / st_w = that conv's weight-gradient input
-            and geometry) -> (g, dy_in, dy_in planes or None).  The IN-backward partials come from the
-            data gradient's epilogue and border add (ops.conv2d_dgrad_refl_in) where it takes
-            the shape; otherwise the two steps run separately."""
+            and geometry; chain: that conv sits in the planes-only chain) -> (g, dy_in, dy_in planes or
+            None).  The IN-backward partials come from the data gradient's epilogue and border add
+            (ops.conv2d_dgrad_refl_in) where it takes the shape; otherwise the two steps run separately."""
             ikf = P["ikf"].get(key)
             cin_p = y_in.shape[-1]
             if DGRAD_EPI and ikf is not None and dy.shape[-1] % 8 == 0:
                 db = mod.bias.grad if (train_w and mod.bias is not None) else None
-                N = x_w.shape[0]
-                want = (train_w and IN_PLANES and
-                        _wgrad_on_bf(N, x_w.shape[1], x_w.shape[2], x_w.shape[3], y_in.shape[1], y_in.shape[2],
-                                     cin_p, R_w, st_w, ops.get_conv_math()))
-                if want and apre and ops.wgrad_nhwc_ok(N, x_w.shape[1], x_w.shape[2], x_w.shape[3], y_in.shape[1],
-                                                       y_in.shape[2], cin_p, R_w, st_w, (R_w - 1) // 2,
-                                                       ops.get_conv_math()):
-                    want = False  # the NHWC-operand weight gradient reads dy_in's NHWC planes (apre)
-                if want and not apre and ops.wgrad_nhwc_f32_ok(N, x_w.shape[1], x_w.shape[2], x_w.shape[3],
-                                                               y_in.shape[1], y_in.shape[2], cin_p, R_w, st_w,
-                                                               (R_w - 1) // 2):
-                    want = False  # ... or dy_in's fp32 itself
+                _, planes, apre = _wgrad_form(x_w.shape, y_in.shape, R_w, st_w, train_w, chain)
                 r = ops.conv2d_dgrad_refl_in(dy, ikf, H, W, cin_p, y_in, s_in, act, 0.0, addend=addend, db=db,
-                                             planes=want, apre=apre)
+                                             planes=planes, apre=apre)
                 if r is not None:
-                    return r if want else (r[0], r[1], None)
+                    return r if planes else (r[0], r[1], None)
             if getattr(dy, "vst_planes_only", False):
                 raise RuntimeError("dgrad_reflect_in: a planes-only gradient reached a route that reads fp32")
             g = dgrad_reflect(dy, key, cin_p, 3, 1, H, W, addend=addend)
-            dyi, pl = in_bwd(g, y_in, s_in, act, mod, x_w, R_w, st_w)
+            dyi, pl = in_bwd(g, y_in, s_in, act, mod, x_w, R_w, st_w, chain=chain)
             return g, dyi, pl
 
         # residual blocks: block i's data gradients each carry the IN backward of the layer below
@@ -788,29 +783,24 @@ class _GeneratorFn(torch.autograd.Function):
         gh = ga
         nb = len(blocks)
         pre_d1 = None
-        # planes-only data-gradient inputs (APRE_BWD) only where every ResnetBlock data gradient takes the epi route
-        # (it reads the planes; the other routes read the fp32 image, which is then not written)
-        apre_bwd = False
-        if APRE_BWD and nb and train_w and DGRAD_EPI:
-            Nb, Hb, Wb, Cb = sv["b0"][0].shape
-            apre_bwd = (Cb % 8 == 0 and all(P["ikf"].get(f"b{i}{c}") is not None for i in range(nb) for c in "ab")
-                        and ops.dgrad_refl_epi_ok(Nb, Hb, Wb, Cb, Cb))
+        # the planes-only chain (the forward's decision): every ResnetBlock conv's dy; not d1's, read as fp32
+        chain = sv["chain"]
         if nb:
             dv, dvp = in_bwd(gh, sv[f"b{nb - 1}"][4], sv[f"b{nb - 1}"][5], "none", blocks[-1].conv_block[5],
-                             sv[f"b{nb - 1}"][3], apre=apre_bwd)
+                             sv[f"b{nb - 1}"][3], chain=chain)
         for i in reversed(range(nb)):
             h, t, s1, uu, v, s2 = sv[f"b{i}"]
             blk = blocks[i].conv_block
             wgrad(blk[5], uu, dv, 3, 1, 1, "reflect", dy_planes=dvp)
             done(blk[5])
             _, dt, dtp = dgrad_reflect_in(dv, f"b{i}b", uu.shape[1], uu.shape[2], t, s1, "relu", blk[1], h, 3, 1,
-                                          apre=apre_bwd)
+                                          chain=chain)
             wgrad(blk[1], h, dt, 3, 1, 1, "reflect", dy_planes=dtp)
             done(blk[1])
             if i > 0:
                 _, _, _, uup, vp, s2p = sv[f"b{i - 1}"]
                 gh, dv, dvp = dgrad_reflect_in(dt, f"b{i}a", h.shape[1], h.shape[2], vp, s2p, "none",
-                                               blocks[i - 1].conv_block[5], uup, 3, 1, addend=gh, apre=apre_bwd)
+                                               blocks[i - 1].conv_block[5], uup, 3, 1, addend=gh, chain=chain)
             else:
                 y1, s1d, _ = sv["d1"]
                 gh, dy1, dyp1 = dgrad_reflect_in(dt, f"b{i}a", h.shape[1], h.shape[2], y1, s1d, "relu", d[1],

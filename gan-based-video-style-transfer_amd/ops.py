@@ -4,8 +4,8 @@ Every function launches on torch's current HIP stream, takes/returns torch tenso
 GPU, and raises on a non-zero status.  Activations are NHWC fp32 with a channel stride that is a
 multiple of 4 (``cpad``); images are NHWC4.  There is no CPU fallback: a CPU tensor is an error.
 """
-import functools
 import os
+import threading
 
 import torch
 
@@ -201,17 +201,25 @@ def _probe_end(h):
 # like this one are route selectors the tests flip in-process to compare routes; they are not read from the
 # environment.)
 FWD_SPLITK = True
-_fws_cache = {}
+
+# Planner answers the step asks for again and again are kept under keys that hold EVERY input of the answer: the
+# inputs given here (shape, arithmetic mode, the route switches read) and the calling thread's tile override — the C
+# override is thread_local and autograd runs the backward on its own thread, so debug_set_tiles mirrors it here.
+_plan_memo = {}
+_tiles = threading.local()
+
+
+def _memo(plan, *inputs):
+    key = (plan.__name__, inputs, getattr(_tiles, "v", None))
+    r = _plan_memo.get(key)
+    if r is None:
+        r = _plan_memo[key] = plan(*inputs)
+    return r
 
 
 def _fwd_ws(N, H, W, Cx, cop, R, S, stride, pad, m, device):
     """Workspace tensor of vst_conv2d_fwd_ws for this shape (None when the launch needs none)."""
-    if not FWD_SPLITK:
-        return None, 0
-    key = (N, H, W, Cx, cop, R, S, stride, pad, m)
-    nb = _fws_cache.get(key)
-    if nb is None:
-        nb = _fws_cache[key] = int(lib().vst_conv2d_fwd_ws_bytes(N, H, W, Cx, cop, R, S, stride, pad, m))
+    nb = _memo(lib().vst_conv2d_fwd_ws_bytes, N, H, W, Cx, cop, R, S, stride, pad, m) if FWD_SPLITK else 0
     if nb == 0:
         return None, 0
     return torch.empty((nb + 3) // 4, device=device), nb
@@ -295,98 +303,93 @@ def conv2d_tfwd(x, wp, bias, Ho, Wo, cx, R, S, stride, pad, act="none", slope=0.
     return y
 
 
-# The weight gradient over the NHWC operands (vst_conv2d_wgrad_nhwc: x fp32 NHWC, dy as its NHWC bf16 planes) where
-# the shape takes it; False: the channel-major operand images of vst_conv2d_wgrad_pre.
+# The four routes of a conv's weight gradient (wgrad_route).  The kernel, and which operand images the layer's
+# producers (the IN apply of x, the IN backward of dy) may write for it, follow from the route alone:
+#   WG_NHWC      vst_conv2d_wgrad_nhwc: x NHWC fp32, dy as its NHWC bf16 planes (``dy.vst_apl``), and only those
+#   WG_NHWC_F32  vst_conv2d_wgrad_nhwc_f32 (its im2col form for short output rows included): x and dy NHWC fp32
+#   WG_IMAGES    vst_conv2d_wgrad_pre on the split-bf16 kernel (WPLAN_BF): the producers may supply x's padded
+#                channel-major image (x_t) and dy's channel-major bf16 planes (dy_planes)
+#   WG_PLAIN     everything else: vst_conv2d_wgrad_pre / _bias, no producer image
+WG_NHWC, WG_NHWC_F32, WG_IMAGES, WG_PLAIN = 0, 1, 2, 3
+# False sends the shapes of WG_NHWC / WG_NHWC_F32 / the im2col form of WG_NHWC_F32 to the routes below them
 WGRAD_NHWC = True
-# ... and with dy fp32 NHWC itself (vst_conv2d_wgrad_nhwc_f32: the stride-2 convs, the ConvTranspose and
-# PatchGAN weight gradients, whose dy has no planes): no operand image at all.
 WGRAD_NHWC_F32 = True
-# ... and its im2col form for output rows shorter than 32 pixels (vst_conv2d_wgrad_nhwc_f32: the StarGAN discriminator's
-# 16x16 / 8x8 / 4x4 layers)
 WGRAD_IM2COL = True
 
 
-@functools.lru_cache(maxsize=512)
-def _wgrad_nhwc_plan_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, math):
-    return bool(lib().vst_conv2d_wgrad_nhwc_ok(N, H, W, Cx, Ho, Wo, Cyp, R, R, stride, pad, math))
+def wgrad_route(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, pad, dy_nhwc_planes=False, role="bwd"):
+    """The route (WG_*) of this conv's weight gradient.  dy_nhwc_planes: dy exists only as its NHWC bf16 planes
+    (the planes-only backward chain) — such a dy can take WG_NHWC and never WG_NHWC_F32.  role: or an arithmetic's
+    name.  The C planners' answer under the calling thread's tile override and the three switches above."""
+    return _memo(_wgrad_route, N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, pad, _math(role), bool(dy_nhwc_planes),
+                 WGRAD_NHWC, WGRAD_NHWC_F32, WGRAD_IM2COL)
 
 
-def wgrad_nhwc_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, policy=None, role="bwd"):
-    """Does vst_conv2d_wgrad_nhwc take this shape under the current policy (policy: accepted for the callers' cache
-    keys; the arithmetic is the current policy's)?"""
-    return WGRAD_NHWC and _wgrad_nhwc_plan_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, _math(role))
+def wgrad_nhwc_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, math="bwd"):
+    """Does a planes-only dy take WG_NHWC at this shape (math: an arithmetic's name, or a role of the policy)?"""
+    return wgrad_route(N, H, W, Cx, Ho, Wo, Cyp, R, R, stride, pad, True, math) == WG_NHWC
 
 
-@functools.lru_cache(maxsize=512)
-def _wgrad_nhwc_f32_plan_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, math):
-    return bool(lib().vst_conv2d_wgrad_nhwc_f32_ok(N, H, W, Cx, Ho, Wo, Cyp, R, R, stride, pad, math))
+def wgrad_nhwc_f32_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, math="bwd"):  # ... and an fp32 dy WG_NHWC_F32?
+    return wgrad_route(N, H, W, Cx, Ho, Wo, Cyp, R, R, stride, pad, False, math) == WG_NHWC_F32
 
 
-def wgrad_nhwc_f32_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, role="bwd"):
-    """... the fp32-dy form (vst_conv2d_wgrad_nhwc_f32, including its im2col form for short output rows): then no
-    operand image need be made for this weight gradient (the producers of x and dy write NHWC fp32 only)."""
-    if not WGRAD_NHWC_F32:
-        return False
-    m = _math(role)
-    return (_wgrad_nhwc_plan_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, m) or
-            (WGRAD_IM2COL and _wgrad_nhwc_f32_plan_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, m)))
+def _wgrad_route(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, pad, m, dy_nhwc_planes, nhwc, nhwc_f32, im2col):
+    geom = (N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, pad, m)
+    if R == S and dy_nhwc_planes:
+        if nhwc and lib().vst_conv2d_wgrad_nhwc_ok(*geom):
+            return WG_NHWC
+    elif R == S and nhwc_f32 and (lib().vst_conv2d_wgrad_nhwc_ok(*geom) or
+                                  (im2col and lib().vst_conv2d_wgrad_nhwc_f32_ok(*geom))):
+        return WG_NHWC_F32
+    return WG_IMAGES if _wgrad_plan(*geom[:10], m)[0] == WPLAN_BF else WG_PLAIN
 
 
 def conv2d_wgrad(x, dy, dw, db, R, S, stride, pad, pad_mode, co, ci, so, si, accumulate=True,
-                 role="bwd", dy_planes=None, x_t=None, dy_apl=None):
+                 role="bwd", dy_planes=None, x_t=None):
     """dw (+)= weight gradient written with strides (so, si) — see vst_conv2d_wgrad; db (if not
     None) (+)= per-channel sum of dy (the bias gradient).  dy_planes: dy's bf16 plane image made by
     instnorm_act_bwd(..., planes=True), x_t: x's padded channel-major image made by
-    instnorm_act_fwd(..., cp=...) (vst_conv2d_wgrad_pre; both used on the x6 split-bf16 path).
-    dy_apl: dy's NHWC bf16 planes (``dy.vst_apl``, instnorm_act_bwd(apre=True)): with x itself (no x_t) the
-    NHWC-operand kernel (vst_conv2d_wgrad_nhwc) where the shape takes it."""
+    instnorm_act_fwd(..., cp=...): those images have one reader, vst_conv2d_wgrad_pre, which then runs.
+    Otherwise the kernel is wgrad_route's, for dy as it arrived (planes-only: ``dy.vst_planes_only``)."""
     _dev_check(x, dy)
     N, H, W, Cx = x.shape
     _, Ho, Wo, Cyp = dy.shape
-    if dy_apl is None and getattr(dy, "vst_planes_only", False) and dy_planes is None:
-        dy_apl = getattr(dy, "vst_apl", None)
-    if (dy_apl is not None and x_t is None and S == R and
-            wgrad_nhwc_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, _policy_name, role)):
-        nbytes = int(lib().vst_conv2d_wgrad_nhwc_ws_bytes(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, pad, _math(role)))
-        ws = torch.empty((nbytes + 3) // 4, device=x.device)
-        h = _probe_begin("wgrad", (N, H, W, Cx, Cyp, R, stride, pad, pad_mode)) if _probes else None
-        _call("vst_conv2d_wgrad_nhwc", _p(x), _p(dy_apl), _p(dw), _p(ws), nbytes, N, H, W, Cx, Ho, Wo, Cyp, R, S, stride,
-              pad, PAD[pad_mode], co, ci, so, si, 1 if accumulate else 0, _math(role), _stream())
-        _probe_end(h)
-        if db is not None:
-            if getattr(dy, "vst_planes_only", False):
-                raise RuntimeError("conv2d_wgrad: the bias gradient of a planes-only dy comes from its IN backward")
-            channel_sum(dy, db, co, accumulate)
-        return
-    if getattr(dy, "vst_planes_only", False) and dy_planes is None:
+    geom = (N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, pad)
+    planes_only = getattr(dy, "vst_planes_only", False)
+    images = x_t is not None or dy_planes is not None
+    route = WG_IMAGES if images else wgrad_route(*geom, dy_nhwc_planes=planes_only, role=role)
+    if planes_only and route == WG_NHWC and db is not None:
+        raise RuntimeError("conv2d_wgrad: the bias gradient of a planes-only dy comes from its IN backward")
+    if planes_only and route != WG_NHWC and dy_planes is None:
         raise RuntimeError("conv2d_wgrad: dy has NHWC planes only and this shape needs its fp32 image / plane copy")
-    if (dy_apl is None and x_t is None and dy_planes is None and S == R and
-            wgrad_nhwc_f32_ok(N, H, W, Cx, Ho, Wo, Cyp, R, stride, pad, role)):
-        nbytes = int(lib().vst_conv2d_wgrad_nhwc_f32_ws_bytes(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, pad, _math(role)))
+    m, acc = _math(role), 1 if accumulate else 0
+    key = (N, H, W, Cx, Cyp, R, stride, pad, pad_mode)
+    if route in (WG_NHWC, WG_NHWC_F32):
+        name = "vst_conv2d_wgrad_nhwc" if route == WG_NHWC else "vst_conv2d_wgrad_nhwc_f32"
+        nbytes = int(getattr(lib(), name + "_ws_bytes")(*geom, m))
         ws = torch.empty((nbytes + 3) // 4, device=x.device)
-        h = _probe_begin("wgrad", (N, H, W, Cx, Cyp, R, stride, pad, pad_mode)) if _probes else None
-        _call("vst_conv2d_wgrad_nhwc_f32", _p(x), _p(dy), _p(dw), _p(ws), nbytes, N, H, W, Cx, Ho, Wo, Cyp, R, S, stride,
-              pad, PAD[pad_mode], co, ci, so, si, 1 if accumulate else 0, _math(role), _stream())
+        h = _probe_begin("wgrad", key) if _probes else None
+        _call(name, _p(x), _p(dy.vst_apl if route == WG_NHWC else dy), _p(dw), _p(ws), nbytes, *geom, PAD[pad_mode],
+              co, ci, so, si, acc, m, _stream())
         _probe_end(h)
         if db is not None:
             channel_sum(dy, db, co, accumulate)
         return
     nbytes = lib().vst_conv2d_wgrad_ws_bytes(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride)
     ws = torch.empty((nbytes + 3) // 4, device=x.device)
-    h = _probe_begin("wgrad", (N, H, W, Cx, Cyp, R, stride, pad, pad_mode)) if _probes else None
-    if db is not None and dy_planes is None and x_t is None:
+    h = _probe_begin("wgrad", key) if _probes else None
+    if db is not None and not images:
         # the weight and bias gradient in one fused pass where a route takes the shape (vst_conv2d_wgrad_bias)
-        rc = lib().vst_conv2d_wgrad_bias(_p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes, N, H, W, Cx, Ho, Wo, Cyp, R, S,
-                                         stride, pad, PAD[pad_mode], co, ci, so, si, 1 if accumulate else 0,
-                                         _math(role), _stream())
+        rc = lib().vst_conv2d_wgrad_bias(_p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes, *geom, PAD[pad_mode], co, ci,
+                                         so, si, acc, m, _stream())
         if rc == 0:
             _probe_end(h)
             return
         if rc != EUNSUPPORTED:
             _lib.check(rc, "vst_conv2d_wgrad_bias")
-    _call("vst_conv2d_wgrad_pre", _p(x), _p(x_t), _p(dy), _p(dy_planes), _p(dw), _p(ws), nbytes, N, H, W, Cx, Ho, Wo,
-          Cyp, R, S, stride, pad, PAD[pad_mode], co, ci, so, si, 1 if accumulate else 0, _math(role),
-          _stream())
+    _call("vst_conv2d_wgrad_pre", _p(x), _p(x_t), _p(dy), _p(dy_planes), _p(dw), _p(ws), nbytes, *geom, PAD[pad_mode],
+          co, ci, so, si, acc, m, _stream())
     _probe_end(h)
     if db is not None:
         channel_sum(dy, db, co, accumulate)
@@ -444,16 +447,14 @@ def _warp_bwd_det(gout, flow, gx, align_corners, masked, negate, cl):
 
 
 def _math(role):
-    from ._lib import MATH_MODES
-    return MATH_MODES[_POLICIES[_policy_name][role]]
+    """VST_MATH_* of a role of the current policy ('fwd' | 'infer' | 'bwd'), or of an arithmetic named outright."""
+    return _lib.MATH_MODES[role if role in _lib.MATH_MODES else _POLICIES[_policy_name][role]]
 
 
 def debug_set_tiles(fprop=-1, tconv=-1, wgrad=-1):
-    """Force GEMM tiles for calls from this host thread (vst_debug_set_tiles; -1 = automatic).  The cached
-    route answers depend on the planner's tiles: dropped."""
-    lib().vst_debug_set_tiles(int(fprop), int(tconv), int(wgrad))
-    _wgrad_nhwc_plan_ok.cache_clear()
-    _wgrad_nhwc_f32_plan_ok.cache_clear()
+    """Force GEMM tiles for calls from this host thread (vst_debug_set_tiles; -1 = automatic)."""
+    _tiles.v = (int(fprop), int(tconv), int(wgrad))
+    lib().vst_debug_set_tiles(*_tiles.v)
 
 
 PLAN_RK, PLAN_SKINNY, PLAN_C4_DIRECT = -1, -2, -3
@@ -464,15 +465,18 @@ TILE_NAMES = {0: "128x128 (8 waves of 64x32)", 1: "128x64", 2: "128x128 (4 waves
               PLAN_C4_DIRECT: "4-channel patch-staged direct kernel"}
 
 
+WPLAN_BF = 2  # VST_WPLAN_BF: the split-bf16 kernel over channel-major operand images
 WPLAN_NAMES = {0: "conv_wgrad_k (NHWC operands)", 1: "copies + conv_wgrad_rk_k", 2: "copies + conv_wgrad_bf_k",
                3: "skinny VALU", 4: "Wo-padded copies + conv_wgrad_bf_k"}
 
 
 def conv_plan_wgrad(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, math):
     """Host-only query (vst_conv_plan_wgrad): (path, tile kind, nsplit) of vst_conv2d_wgrad."""
+    return _wgrad_plan(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, _math(math))
+
+
+def _wgrad_plan(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, m):
     import ctypes
-    from ._lib import MATH_MODES
-    m = MATH_MODES[math] if math in MATH_MODES else _math(math)
     path, kind, ns = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     _call("vst_conv_plan_wgrad", N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, m, ctypes.addressof(path),
           ctypes.addressof(kind), ctypes.addressof(ns))
@@ -482,8 +486,7 @@ def conv_plan_wgrad(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, math):
 def conv_plan_fwd_tail(N, H, W, Cx, Cop, R, S, stride, pad, math):
     """Host-only: split-K count of the x6 tail launch vst_conv2d_fwd_ws runs for this shape (0: none)."""
     import ctypes
-    from ._lib import MATH_MODES
-    m = MATH_MODES[math] if math in MATH_MODES else _math(math)
+    m = _math(math)
     ks = ctypes.c_int(0)
     _call("vst_conv_plan_fwd_tail", N, H, W, Cx, Cop, R, S, stride, pad, m, ctypes.addressof(ks))
     return ks.value
@@ -494,8 +497,7 @@ def conv_plan_fwd(N, H, W, Cx, Cop, R, S, stride, pad_h, pad_w, math, with_tail=
     would use for this shape under `math` ('fp32' | 'bf16x3' | 'bf16x6', or a role of the current
     policy)."""
     import ctypes
-    from ._lib import MATH_MODES
-    m = MATH_MODES[math] if math in MATH_MODES else _math(math)
+    m = _math(math)
     kind, ms, tk = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     _call("vst_conv_plan_fwd", N, H, W, Cx, Cop, R, S, stride, pad_h, pad_w, m, ctypes.addressof(kind),
           ctypes.addressof(ms), ctypes.addressof(tk))
@@ -1288,6 +1290,13 @@ def tap_conv_fwd_h(x, sok, bias, R, pad, pad_mode="zero", act="none", slope=0.0,
     return y
 
 
+def tap_conv_wgrad_bf_ok(x, R, role="bwd"):
+    """Does tap_conv_wgrad's own GEMM (the 1x1 weight gradient of the 4 R R folded dy channels against x) run on
+    the split-bf16 kernel, which reads x's unpadded channel-major image (x_t) and the folded dy as planes?"""
+    N, H, W, Cx = x.shape
+    return conv_plan_wgrad(N, H, W, Cx, H, W, R * R * 4, 1, 1, 1, role)[0] == WPLAN_BF
+
+
 def tap_conv_wgrad(x, dy, dw, R, pad, pad_mode="zero", accumulate=True, role="bwd", x_t=None):
     """dw [Co<=4][Ci][R][R] (+)= weight gradient of tap_conv_fwd given dy NHWC4 (pre-activation).
     x_t: x's unpadded channel-major image (instnorm_act_fwd(cp=(0, "zero", 1))) for the x6 path."""
@@ -1295,7 +1304,7 @@ def tap_conv_wgrad(x, dy, dw, R, pad, pad_mode="zero", accumulate=True, role="bw
     N, H, W, Cx = x.shape
     Co, Ci = dw.shape[0], dw.shape[1]
     K = R * R * 4
-    if TAP_PLANES and TAP_CHUNK_BYTES <= 0 and conv_plan_wgrad(N, H, W, Cx, H, W, K, 1, 1, 1, role)[0] == 2:
+    if TAP_PLANES and TAP_CHUNK_BYTES <= 0 and tap_conv_wgrad_bf_ok(x, R, role):
         # D straight as the x6 wgrad's bf16 planes (vst_tapfold_planes): no fp32 D, no plane copy
         P = N * H * W
         ldp = lib().vst_cp_ld(P)
@@ -1323,7 +1332,7 @@ def tap_conv_wgrad_h_ok(x, R, pad, pad_mode, role="bwd"):
     runs on the x6 split-bf16 kernel without padded rows."""
     N, H, W, Cx = x.shape
     return (pad_mode == "reflect" and 2 * pad == R - 1 and pad + 1 < min(H, W) and
-            conv_plan_wgrad(N, H, W, Cx, H + 2, W + R + 1, 4 * R, R, 1, 1, role)[0] == 2)
+            conv_plan_wgrad(N, H, W, Cx, H + 2, W + R + 1, 4 * R, R, 1, 1, role)[0] == WPLAN_BF)
 
 
 def tap_conv_wgrad_h(x, dy, dw, R, pad, pad_mode="reflect", accumulate=True, role="bwd", x_t=None):
@@ -1362,7 +1371,7 @@ def tap_conv_wgrad_swap_ok(x, R, pad, pad_mode, role="bwd", co=4):
     wx, Wq = tap_swap_geom(W, R)
     cx = 3 if co <= 3 else 4
     return (TAP_SWAP and pad_mode == "reflect" and 2 * pad == R - 1 and pad < min(H, W) and Cx % 4 == 0 and
-            conv_plan_wgrad(N, H, W + wx, cx, H + R - 1, Wq, Cx, R, R, 1, role)[0] == 2)
+            conv_plan_wgrad(N, H, W + wx, cx, H + R - 1, Wq, Cx, R, R, 1, role)[0] == WPLAN_BF)
 
 
 def tap_conv_wgrad_swap(x, dy, dw, R, pad, pad_mode="reflect", accumulate=True, role="bwd", x_pl=None, db=None):

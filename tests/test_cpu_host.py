@@ -273,3 +273,114 @@ def test_convflops_counter_wraps_live_ops():
     assert not missing, missing
     with convflops.Counter():
         pass
+
+
+def _generator_wgrad_layers(N, H, W, ngf=64):
+    """name -> (N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, pad) of the ResnetGenerator's conv weight gradients."""
+    h2, w2 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    h4, w4 = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
+    d0 = (N, H, W, ngf, h2, w2, 2 * ngf, 3, 3, 2, 1)
+    d1 = (N, h2, w2, 2 * ngf, h4, w4, 4 * ngf, 3, 3, 2, 1)
+    return {"c0_4": (N, H, W, 4, H, W, ngf, 7, 7, 1, 3), "c0_8": (N, H, W, 8, H, W, ngf, 7, 7, 1, 3),
+            "d0": d0, "d1": d1, "res": (N, h4, w4, 4 * ngf, h4, w4, 4 * ngf, 3, 3, 1, 1),
+            "u0": d1, "u1": d0,  # the ConvTranspose layers' equivalent convs
+            "f": (N, H, W, ngf, H, W, 4, 7, 7, 1, 3)}
+
+
+def _patchgan_wgrad_layers(N, H, W, ndf=64):
+    out, cin, c = {}, 4, ndf
+    for i, st in enumerate((2, 2, 2, 1, 1)):
+        cout = 4 if i == 4 else c
+        Ho, Wo = (H + 2 - 4) // st + 1, (W + 2 - 4) // st + 1
+        out["D%d" % i] = (N, H, W, cin, Ho, Wo, cout, 4, 4, st, 1)
+        H, W, cin, c = Ho, Wo, cout, min(2 * c, 8 * ndf)
+    return out
+
+
+# The routes of the production layers, N = NHWC planes, F = NHWC fp32 dy, I = operand images, P = plain: what the
+# predicates this function replaced (wgrad_nhwc_ok, wgrad_nhwc_f32_ok, the VST_WPLAN_BF plan query, in that
+# precedence) answered on this library before the change.  "res" with an fp32 dy; "res_chain" in the planes-only
+# chain.  C2 (ngf = ndf = 64, 256^2, N = 8 and 12) and C3 (1 x 436 x 1024) agree layer by layer.
+_ROUTES_X6 = dict(c0_4="I", c0_8="I", d0="F", d1="F", res="F", res_chain="N", u0="F", u1="F", f="P",
+                  D0="I", D1="F", D2="F", D3="P", D4="P")
+_STARGAN_D = [  # tests/test_gpu_wgrad_nhwc.py IM2COL_CASES: N, H, W, Cx, Cyp, R, stride, pad -> fp32 dy / planes-only dy
+    ((4, 32, 32, 256, 512, 4, 2, 1), "FI"), ((4, 16, 16, 512, 1024, 4, 2, 1), "FI"),
+    ((4, 8, 8, 1024, 2048, 4, 2, 1), "FP"), ((2, 16, 16, 64, 128, 3, 1, 1), "FI")]
+
+
+def test_wgrad_route_pinned_for_production_layers():
+    import gbvst
+    from gbvst import ops
+    gbvst._lib.load()
+    letter = {ops.WG_NHWC: "N", ops.WG_NHWC_F32: "F", ops.WG_IMAGES: "I", ops.WG_PLAIN: "P"}
+    prev = ops.get_conv_math()
+    try:
+        for policy in ("bf16x6", "mixed", "fp32"):
+            ops.set_conv_math(policy)
+            for cfg in ((8, 256, 256), (12, 256, 256), (1, 436, 1024)):
+                layers = dict(_generator_wgrad_layers(*cfg), **_patchgan_wgrad_layers(*cfg))
+                got = {k: letter[ops.wgrad_route(*g)] for k, g in layers.items()}
+                got["res_chain"] = letter[ops.wgrad_route(*layers["res"], True)]
+                # mixed and fp32 gradients decline both NHWC routes and the split-bf16 kernel: all plain
+                want = _ROUTES_X6 if policy == "bf16x6" else dict.fromkeys(_ROUTES_X6, "P")
+                assert got == want, (policy, cfg, {k: (got[k], want[k]) for k in got if got[k] != want[k]})
+            for (N, H, W, Cx, Cyp, R, st, pad), want in _STARGAN_D:
+                Ho, Wo = (H + 2 * pad - R) // st + 1, (W + 2 * pad - R) // st + 1
+                g = (N, H, W, Cx, Ho, Wo, Cyp, R, R, st, pad)
+                got = letter[ops.wgrad_route(*g)] + letter[ops.wgrad_route(*g, True)]
+                assert got == (want if policy == "bf16x6" else "PP"), (policy, g, got)
+    finally:
+        ops.set_conv_math(prev)
+
+
+def test_wgrad_route_follows_the_calling_threads_tile_override():
+    """The tile override is per host thread (autograd runs the backward on its own): a route answer is the C
+    planner's answer in the thread that asks, under an override and after its reset."""
+    import threading
+    import gbvst
+    from gbvst import ops
+    lib = gbvst._lib.load()
+    g = (8, 64, 64, 256, 64, 64, 256, 3, 3, 1, 1)
+    prev = ops.set_conv_math("bf16x6")
+
+    def both():  # (Python route says WG_NHWC, the C planner says yes) in the calling thread
+        return (ops.wgrad_route(*g, True) == ops.WG_NHWC,
+                bool(lib.vst_conv2d_wgrad_nhwc_ok(*g, gbvst._lib.MATH_MODES["bf16x6"])))
+
+    def in_thread():
+        out = []
+        t = threading.Thread(target=lambda: out.append(both()))
+        t.start()
+        t.join()
+        return out[0]
+
+    try:
+        assert both() == (True, True)  # (and a warm answer, were one kept)
+        ops.debug_set_tiles(-1, -1, 1)
+        try:
+            here, there = both(), in_thread()
+            assert here[0] == here[1] and there[0] == there[1]
+            assert there == (True, True) and here == (False, False)  # the override reaches this thread only
+        finally:
+            ops.debug_set_tiles(-1, -1, -1)
+        assert both() == in_thread() == (True, True)
+    finally:
+        ops.set_conv_math(prev)
+
+
+def test_route_overrides_reject_malformed_arms(monkeypatch):
+    from gbvst import _lib
+    g = {"TAP_H": True, "WGRAD_NHWC": True}
+    for spec in ("netwroks.TAP_H=0", "ops.WGRAD_NHWC", "ops.WGRAD_NHWC=0,netwroks.TAP_H=0"):
+        monkeypatch.setenv("VST_ROUTES", spec)
+        for module in ("gbvst.ops", "gbvst.networks"):
+            with pytest.raises(ValueError):
+                _lib.apply_route_overrides(module, dict(g))
+    monkeypatch.setenv("VST_ROUTES", "ops.WGRAD_NHWC=0,networks.TAP_H=0")
+    go, gn = dict(g), dict(g)
+    _lib.apply_route_overrides("gbvst.ops", go)
+    _lib.apply_route_overrides("gbvst.networks", gn)
+    assert go == {"TAP_H": True, "WGRAD_NHWC": False} and gn == {"TAP_H": False, "WGRAD_NHWC": True}
+    monkeypatch.setenv("VST_ROUTES", "ops.NO_SUCH_FLAG=0")
+    with pytest.raises(ValueError):
+        _lib.apply_route_overrides("gbvst.ops", dict(g))

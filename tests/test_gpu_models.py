@@ -285,3 +285,108 @@ def test_graphed_inference_matches_eager(gb):
             y = net(x)
             assert next(iter(net._graphs)) == key      # same captured graph, refreshed packs
             assert torch.equal(y, net._forward_eager(x))
+
+
+# ------------------------------------------------------------------------------------------------
+# The weight-gradient routes and producer forms of one generator (ops.wgrad_route, networks._wgrad_form)
+# under every route switch: ngf=32, 2 blocks at 2x3x128x128 is the smallest generator whose layers take
+# all four routes (ngf=16 or a 64x64 input loses the NHWC routes).
+_ROUTE_ARMS = {
+    "default": (),
+    "no_wgrad_nhwc": (("ops", "WGRAD_NHWC"),),
+    "no_in_planes": (("networks", "IN_PLANES"),),
+    "no_wgrad_nhwc_no_in_planes": (("ops", "WGRAD_NHWC"), ("networks", "IN_PLANES")),
+    "no_apre_bwd": (("networks", "APRE_BWD"),),
+    "no_dgrad_epi": (("networks", "DGRAD_EPI"),),
+    "no_wgrad_nhwc_f32": (("ops", "WGRAD_NHWC_F32"),),
+    "no_in_xt": (("networks", "IN_XT"),),
+}
+# not bit-equal to the default arm by construction: DGRAD_EPI=False replaces the IN-backward reduction taken
+# in the data gradient's epilogue by a separate reduction pass; APRE_BWD=False stages the data gradient's dy
+# operand from fp32 rather than from pre-split planes
+_ROUTE_ARMS_OTHER_BITS = ("no_dgrad_epi", "no_apre_bwd")
+_ROUTE_NGF, _ROUTE_NB, _ROUTE_SHAPE = 32, 2, (2, 3, 128, 128)
+
+
+def _route_net_run(gb, net, x0, gy):
+    net.zero_grad()
+    x = x0.clone().requires_grad_(True)
+    y = net(x)
+    y.backward(gy)
+    torch.cuda.synchronize()
+    return y.detach().cpu(), x.grad.cpu(), {k: p.grad.detach().clone() for k, p in net.named_parameters()}
+
+
+@pytest.fixture(scope="module")
+def route_case(gb):
+    """The network, its inputs, the float64 CPU oracle's (y, dx, parameter gradients) and the default arm's
+    parameter gradients, computed once."""
+    from gbvst import networks, ops
+    from oracle import cpu_ref, prng
+    ref = cpu_ref.RefResnetGenerator(3, 3, _ROUTE_NGF, _ROUTE_NB)
+    sd = prng.init_state_dict(cpu_ref.state_shapes(ref), base_seed=611)
+    cpu_ref.load_np_state(ref, sd)
+    ref.double()
+    x = torch.from_numpy(prng.uniform_f32(612, _ROUTE_SHAPE, -1, 1))
+    gy = torch.from_numpy(prng.uniform_f32(613, _ROUTE_SHAPE, -1, 1))
+    xr = x.double().requires_grad_(True)
+    yr = ref(xr)
+    yr.backward(gy.double())
+    oracle = (yr.detach().numpy(), xr.grad.numpy(), {k: p.grad.numpy() for k, p in ref.named_parameters()})
+    net = networks.ResnetGenerator(3, 3, ngf=_ROUTE_NGF, norm_layer=networks.get_norm_layer('instance'),
+                                   n_blocks=_ROUTE_NB).to(DEV)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    prev = ops.set_conv_math("bf16x6")
+    try:
+        default = _route_net_run(gb, net, x.to(DEV), gy.to(DEV))[2]
+    finally:
+        ops.set_conv_math(prev)
+    return net, x.to(DEV), gy.to(DEV), oracle, default
+
+
+@pytest.mark.parametrize("arm", list(_ROUTE_ARMS))
+def test_generator_routes_vs_oracle(gb, route_case, arm):
+    """Every route switch leaves the generator's forward + backward running, within the network bounds of the
+    float64 oracle (1e-4 output and input gradient, 1e-3 parameter gradients, relative to max|ref|), and —
+    the routes being bit-identical op by op — every parameter gradient bit-equal to the default arm's."""
+    from gbvst import networks, ops
+    net, x, gy, (y_ref, dx_ref, g_ref), default = route_case
+    mods = {"ops": ops, "networks": networks}
+    prev_math = ops.set_conv_math("bf16x6")
+    prev = [(m, f, getattr(mods[m], f)) for m, f in _ROUTE_ARMS[arm]]
+    try:
+        # the guard: with every switch on, these layers take the four routes (a planner change must not
+        # silently turn this into a test of one route)
+        N, ngf = _ROUTE_SHAPE[0], _ROUTE_NGF
+        d0 = (N, 128, 128, ngf, 64, 64, 2 * ngf, 3, 3, 2, 1)      # also the last ConvTranspose's equivalent conv
+        d1 = (N, 64, 64, 2 * ngf, 32, 32, 4 * ngf, 3, 3, 2, 1)    # also the first ConvTranspose's
+        res = (N, 32, 32, 4 * ngf, 32, 32, 4 * ngf, 3, 3, 1, 1)
+        assert ops.wgrad_route(*res, True) == ops.WG_NHWC and ops.dgrad_refl_epi_ok(N, 32, 32, 4 * ngf, 4 * ngf)
+        assert networks._rb_wgrad_nhwc(N, 32, 32, 4 * ngf)
+        assert ops.wgrad_route(*d1) == ops.WG_NHWC_F32 and ops.wgrad_route(*d0) == ops.WG_IMAGES
+        for cx in (4, 8):
+            assert ops.wgrad_route(N, 128, 128, cx, 128, 128, ngf, 7, 7, 1, 3) == ops.WG_IMAGES
+        assert networks.TAP_LAST and ops.tap_conv_wgrad_swap_ok(torch.empty((N, 128, 128, ngf), device="meta"), 7, 3,
+                                                                "reflect", co=3)
+        for m, f in _ROUTE_ARMS[arm]:
+            setattr(mods[m], f, False)
+        y, dx, grads = _route_net_run(gb, net, x, gy)
+    finally:
+        for m, f, v in prev:
+            setattr(mods[m], f, v)
+        ops.set_conv_math(prev_math)
+    e_y, e_dx = _rel(y, y_ref), _rel(dx, dx_ref)
+    print(arm, "rel err: y %.3g dx %.3g" % (e_y, e_dx))
+    assert e_y < 1e-4 and e_dx < 1e-4, (e_y, e_dx)
+    real_bias = "model.%d.bias" % (17 + _ROUTE_NB)  # the last conv's: every other bias feeds an InstanceNorm
+    for k, g in grads.items():
+        if k.endswith("bias") and k != real_bias:
+            # biases in front of InstanceNorm: exact gradient is 0, both sides are rounding noise
+            assert g.abs().max().item() < 1e-3, k
+        else:
+            e = _rel(g.cpu(), g_ref[k])
+            print(arm, k, "rel err %.3g" % e)
+            assert e < 1e-3, (k, e)
+    if arm not in _ROUTE_ARMS_OTHER_BITS:
+        diff = [k for k, g in grads.items() if not torch.equal(g, default[k])]
+        assert not diff, (arm, {k: (grads[k] - default[k]).abs().max().item() for k in diff})
