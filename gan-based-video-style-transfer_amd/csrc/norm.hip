@@ -768,7 +768,7 @@ extern "C" int vst_instnorm_stats(const float* x, float* stats, float* ws, int N
                                   float eps, void* stream) {
   RedGeom g;
   VST_REQUIRE(x && stats && ws && N > 0 && HW > 0 && red_geom(N, HW, C, g),
-              "instnorm_stats: bad args (C must be 4*2^k <= 1024)");
+              "instnorm_stats: bad args (C must be a multiple of 4, at most 1024)");
   hipStream_t s = (hipStream_t)stream;
   double* part = reinterpret_cast<double*>(ws);
   hipLaunchKernelGGL(in_partial_k<0>, dim3(g.nsplit, N), dim3(NRED), 0, s, x, (const float*)nullptr,
@@ -1020,7 +1020,7 @@ extern "C" int vst_instnorm_affine_bwd(const float* gy, const float* x, const fl
                                        int act, float slope, int accumulate, void* stream) {
   RedGeom g;
   VST_REQUIRE(gy && x && stats && gamma && beta && dx && ws && red_geom(N, HW, C, g),
-              "instnorm_affine_bwd: bad args (C must be 4*2^k <= 1024)");
+              "instnorm_affine_bwd: bad args (C must be a multiple of 4, at most 1024)");
   hipStream_t s = (hipStream_t)stream;
   double* part = reinterpret_cast<double*>(ws);
   char* p = reinterpret_cast<char*>(ws) + (size_t)N * g.nsplit * C * 4 * sizeof(double);

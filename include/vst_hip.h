@@ -328,7 +328,7 @@ int vst_instnorm_act_fwd(const float* x, const float* stats, const float* residu
 /* Backward of y = act(IN(x)):  dx = rstd * (g - mean(g) - xhat * mean(g*xhat)),
  * g = gy * act'(xhat).  db (NULL or C floats) receives (accumulate_db: adds) sum_{n,p} dx — the
  * gradient of a conv bias feeding this IN — from the same fp64 reduction (no extra pass).
- * ws: vst_instnorm_ws_bytes bytes.  C must be 4*2^k <= 1024. */
+ * ws: vst_instnorm_ws_bytes bytes.  C must be a multiple of 4, at most 1024. */
 int vst_instnorm_act_bwd(const float* gy, const float* x, const float* stats, float* dx, float* db,
                          float* ws, int N, int HW, int C, int act, float slope, int accumulate_db,
                          void* stream);
@@ -457,7 +457,7 @@ int vst_resize_bilinear(const float* x, const float* mult, float* y, int N, int 
                         int Wo, void* stream);
 /* Affine instance norm: y = s * act(gamma[c] * xhat + beta[c]) + residual, with stats from
  * vst_instnorm_stats; s = 1 (gate NULL) or s = 2|u|/(1+|u|), u = gate_mult * gate[0] (device scalar:
- * ResidualBlock layer_strength, network.py:241-245).  residual may be NULL.  C = 4*2^k <= 1024. */
+ * ResidualBlock layer_strength, network.py:241-245).  residual may be NULL.  C a multiple of 4, at most 1024. */
 int vst_instnorm_affine_fwd(const float* x, const float* stats, const float* gamma, const float* beta,
                             const float* gate, float gate_mult, const float* residual, float* y,
                             int N, int HW, int C, int act, float slope, void* stream);

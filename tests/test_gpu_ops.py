@@ -3,7 +3,11 @@ the same inputs) and against the reference-generated golden fixtures.  Tolerance
 test: convs compare with |err| <= tol * max|ref| + 1e-6 with tol = 2e-5 under VST_MATH_F32 (fp32
 MFMA is an exact fp32 fma chain; only the summation order differs from the CPU) and 1e-4 under
 VST_MATH_BF16X3 (split-operand bf16 products, <= ~2^-16 relative each); elementwise/flow ops 1e-5
-absolute."""
+absolute.
+
+The reduction families (InstanceNorm stats / forward / backward in every slice geometry, affine
+InstanceNorm, running statistics, the scalar losses and axpby) are checked per plane against fp64
+references in tests/test_gpu_reductions.py; this file keeps one shape of each."""
 import numpy as np
 import pytest
 import torch
