@@ -120,6 +120,11 @@ SIGNATURES = {
     "vst_temporal_sqdiff_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, P]),
     "vst_temporal_sqdiff_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, P]),
     "vst_resize_bilinear": (I, [P, P, P, I, I, I, I, I, I, P]),
+    "vst_ruder_stack_fwd": (I, [P, P, P, P, P, P, I, I, I, F, P]),
+    "vst_ruder_stack_bwd": (I, [P, P, P, P, P, I, I, I, F, P]),
+    "vst_ruder_temporal_part_floats": (I, [I, I, I]),
+    "vst_ruder_temporal_fwd": (I, [P, P, P, P, P, I, I, I, F, F, P]),
+    "vst_ruder_temporal_bwd": (I, [P, P, P, P, P, P, I, I, I, F, F, P]),
     "vst_instnorm_affine_fwd": (I, [P, P, P, P, P, F, P, P, I, I, I, I, F, P]),
     "vst_instnorm_affine_ws_bytes": (SZ, [I, I, I]),
     "vst_instnorm_affine_bwd": (I, [P, P, P, P, P, P, F, P, P, P, P, P, P, I, I, I, I, F, I, P]),

@@ -118,7 +118,7 @@ class ResidualBlock(nn.Module):
 
 class FastStyleNet(FlatNet):
     """network.py:263-298.  forward(x, style_strength=1.0, s_id=0) -> (features, image), NCHW;
-    x is the [0, 1] image (3 channels, or 7 for the ReCoNet-style stacked input)."""
+    x is the [0, 1] image (3 channels, or 7 for Ruder's stacked input: frame, mask, warped previous frame)."""
 
     def __init__(self, num_inp, n_styles=1):
         super().__init__()
@@ -494,6 +494,123 @@ class Reconet(_VideoFastStyle):
         tv = perceptual.tv_loss_nhwc(styled, self.delta / 2.0 / 255.0, 3)
         loss = content + style + f_temporal + o_temporal + tv
         return loss, content, style, f_temporal, o_temporal, tv, styled
+
+
+class Ruder(Johnson):
+    """fs_ruder.py:10-121: the recurrent video method.  Frame k is styled by ``model`` (FastStyleNet(7, 1)) from
+    cat(frame_k, mask_{k-1}, fs_lib.warp(styled_{k-1} / 255, flow_{k-1})); frame 1 by the frozen
+    ``pre_style_model`` (FastStyleNet(3, 1), a trained Johnson net).  The recurrence runs for 2, 3 or 5 frames,
+    the losses are taken on the last frame only, and their gradient runs back through every warp and every
+    earlier application of ``model`` down to styled frame 1, where it stops: Adam covers ``model`` only
+    (fast_style_transfer.py:226) and the pre-style net runs under no_grad.
+    emphasis = (alpha, beta, gamma): content, style and temporal weights."""
+
+    def __init__(self, style_imgs, emphasis=(1.0, 1e5, 1e2), lr=1e-3, batch_sz=16, device="cuda", vgg=None,
+                 model=None, pre_style_model=None):
+        alpha, beta, self.gamma = emphasis
+        dev = torch.device(device)
+        if model is None:
+            model = FastStyleNet(7, 1).to(dev)
+        super().__init__(style_imgs, (alpha, beta, 0.0), lr, batch_sz, device, vgg, model)
+        self.pre_style_model = pre_style_model if pre_style_model is not None else FastStyleNet(3, 1).to(dev)
+
+    @staticmethod
+    def roll(p=0.5):
+        """fs_ruder.py:18-19: one np.random.random() draw."""
+        import numpy as np
+        return bool(np.random.random() < p)
+
+    @staticmethod
+    def n_recurrent(n_imgs):
+        """Index of the loss frame for ``n_imgs`` frames (fs_ruder.py:52-75): the ``len > 2`` and ``len > 4``
+        branches make it 1, 2 or 4 (2, 3 or 5 frames used; 4 frames behave as 3)."""
+        if n_imgs < 2:
+            raise ValueError("Ruder: at least two frames, got %d" % n_imgs)
+        return 4 if n_imgs > 4 else 2 if n_imgs > 2 else 1
+
+    def losses_nhwc(self, frames, masks, flows, roll):
+        """train_method's loss graph (fs_ruder.py:38-108).  frames: list of NHWC4 [0,1] batches; masks: list of
+        [B,1,H,W] planes; flows: list of [B,2,H,W] planes (pair k-1 leads from frame k-1 to frame k).
+
+        Returns (total, style, content, temporal, styled frame 2 as NHWC4 0..255): the REFERENCE's tuple order
+        (fs_ruder.py:103 packs style before content although its labels name content first).  The temporal term
+        is weighted by the LAST plane of ``masks`` (``masks[-1]``, fs_ruder.py:97) whichever frame the loss is
+        taken on; without ``roll`` frame 2 is styled from the blank input (fs_ruder.py:78) and the temporal loss
+        is a device zero."""
+        if roll:
+            last = self.n_recurrent(len(frames))
+            if len(masks) < last or len(flows) < last:
+                raise ValueError("Ruder: %d frames need %d mask / flow planes, got %d / %d" %
+                                 (last + 1, last, len(masks), len(flows)))
+            with torch.no_grad():
+                _, y = self.pre_style_model.forward_nhwc(frames[0])
+            styled2 = None
+            for k in range(1, last + 1):
+                x, w = fs_lib.ruder_stack_nhwc(y, frames[k], flows[k - 1], masks[k - 1])
+                _, y = self.model.forward_nhwc(x)
+                if k == 1:
+                    styled2 = y
+            loss_img = frames[last]
+            temporal = fs_lib.ruder_temporal_nhwc(w, y, masks[-1], self.gamma)
+        else:
+            _, y = self.model.forward_nhwc(fs_lib.ruder_blank_nhwc(frames[1]))
+            styled2, loss_img = y, frames[1]
+            temporal = torch.zeros((), device=y.device)
+        with torch.no_grad():
+            xc = perceptual.normalize_nhwc(loss_img)
+        styled_f, img_f = self.vgg.forward_multi_nhwc([perceptual.normalize_nhwc(y, d0=255.0), xc],
+                                                      [len(self.vgg.slices_idx), 3])
+        content = perceptual.mse_loss(styled_f[2], img_f[2], self.alpha)
+        style = None
+        for f, gs in zip(styled_f, self._style_targets(loss_img.shape[0])):
+            t = perceptual.mse_loss(perceptual.gram_nhwc(f), gs, self.beta)
+            style = t if style is None else style + t
+        loss = content + style + temporal
+        return loss, style, content, temporal, styled2
+
+    def train_step(self, imgs, masks, flows, roll=None):
+        """imgs: list of [B,3,H,W] frames in [0,1]; masks [B,k,H,W]; flows [B,2k,H,W] (the reference's layout).
+        roll None: drawn as fs_ruder.py:44 does (np.random.random() < 0.5, one draw per step).  prep_adam +
+        train_method + adam.step; returns ((total, style, content, temporal) as device scalars, in the reference's
+        order) and styled frame 2 (NHWC4, 0..255)."""
+        if roll is None:
+            roll = self.roll(0.5)
+        self.prep_adam(self.itr)
+        dev = self.device
+        frames = [ops.nchw_to_nhwc(i.to(dev).float().contiguous()) for i in imgs]
+        masks = masks.to(dev).float()
+        flows = flows.to(dev).float()
+        mlist = [masks[:, k:k + 1].contiguous() for k in range(masks.shape[1])]
+        flist = [flows[:, 2 * k:2 * k + 2].contiguous() for k in range(flows.shape[1] // 2)]
+        out = self.losses_nhwc(frames, mlist, flist, roll)
+        out[0].backward()
+        self.adam.step()
+        self.itr += 1
+        return tuple(v.detach() for v in out[:-1]), out[-1].detach()
+
+    @torch.no_grad()
+    def infer_method(self, params):
+        """fs_ruder.py:110-121 on NCHW tensors: params = (frame, mask, warped).  mask None: the pre-style net
+        on the frame alone (first frame); else model(cat(frame, mask, warped)).  Styled frame / 255."""
+        frame, mask, warped = (tuple(params) + (None, None))[:3]
+        dev = self.device
+        frame = frame.to(dev).float()
+        if mask is None:
+            _, styled = self.pre_style_model(frame)
+        else:
+            _, styled = self.model(torch.cat((frame, mask.to(dev).float(), warped.to(dev).float()), 1))
+        return styled / 255.0
+
+    @torch.no_grad()
+    def stylize_next(self, prev_styled_nhwc, frame_nhwc, flow, mask):
+        """One device-resident recurrence step of video inference: the previous styled frame (NHWC4, 0..255) is
+        warped by ``flow``, stacked with the next frame (NHWC4, [0,1]) and ``mask`` by one kernel and styled;
+        returns the styled frame (NHWC4, 0..255), ready to be the next call's ``prev_styled_nhwc``."""
+        dev = self.device
+        x, _ = ops.ruder_stack(prev_styled_nhwc.contiguous(), frame_nhwc.contiguous(),
+                               flow.to(dev).float().contiguous(), mask.to(dev).float().contiguous(), want_w=False)
+        _, styled = self.model.forward_nhwc(x)
+        return styled
 
 
 from . import _lib as _lib_routes  # noqa: E402

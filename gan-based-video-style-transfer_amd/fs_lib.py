@@ -90,3 +90,64 @@ def temporal_loss_pair_nhwc(ab, flow, mask, scale, inputs=None, ab_scale=1.0, cl
     flow, mask, i1, i2 = _temporal_args(flow, mask, inputs)
     return _TemporalLossNHWC.apply(ab.contiguous(), None, flow, mask, float(scale), float(ab_scale), cl, i1, i2,
                                    True)
+
+
+class _RuderStackNHWC(torch.autograd.Function):
+    """The recurrent input of fs_ruder.py:52 as one node with two outputs: x, the net's 8-channel-padded input,
+    and w, the warped previous frame the temporal loss reads.  Differentiable in y_prev only; the backward takes
+    both output gradients (the net's input gradient and the temporal loss's) in ONE scatter, so autograd never
+    adds two image tensors."""
+
+    @staticmethod
+    def forward(ctx, y_prev, img, flow, mask, scale):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(flow)
+        ctx.scale = scale
+        return ops.ruder_stack(y_prev, img, flow, mask, scale)
+
+    @staticmethod
+    def backward(ctx, gx, gw):
+        if not ctx.needs_input_grad[0] or (gx is None and gw is None):
+            return None, None, None, None, None
+        (flow,) = ctx.saved_tensors
+        gx = None if gx is None else gx.contiguous()
+        gw = None if gw is None else gw.contiguous()
+        N, _, H, W = flow.shape
+        gy = torch.zeros((N, H, W, 4), device=flow.device, dtype=torch.float32)
+        ops.ruder_stack_bwd(gx, gw, flow, gy, ctx.scale)
+        return gy, None, None, None, None
+
+
+def ruder_stack_nhwc(y_prev, img, flow, mask, scale=1.0 / 255.0):
+    """(x, w): x [B,H,W,8] = (img rgb, mask, warp(scale * y_prev, flow) rgb, 0), the Ruder net's input for the next
+    frame (fs_ruder.py:52), and w [B,H,W,4] = the same warped frame.  y_prev: previous styled frame, NHWC4 0..255;
+    img NHWC4 [0,1]; flow [B,2,H,W]; mask [B,1,H,W].  Differentiable in y_prev only."""
+    return _RuderStackNHWC.apply(y_prev.contiguous(), img.detach().contiguous(), flow.detach().contiguous().float(),
+                                 mask.detach().contiguous().float(), float(scale))
+
+
+def ruder_blank_nhwc(img):
+    """The input of the branch without a previous frame (fs_ruder.py:78): (img rgb, 0, 0, 0, 0, 0), [B,H,W,8]."""
+    return ops.ruder_stack(None, img.detach().contiguous(), None, None, want_w=False)[0]
+
+
+class _RuderTemporalNHWC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w, y, mask, scale, ab_scale):
+        ctx.save_for_backward(w, y, mask)
+        ctx.conf = (scale, ab_scale)
+        return ops.ruder_temporal(w, y, mask, scale, ab_scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        w, y, mask = ctx.saved_tensors
+        gw, gy = ops.ruder_temporal_bwd(w, y, mask, g.contiguous(), *ctx.conf, need_w=ctx.needs_input_grad[0],
+                                        need_y=ctx.needs_input_grad[1])
+        return gw, gy, None, None, None
+
+
+def ruder_temporal_nhwc(w, y, mask, scale, ab_scale=1.0 / 255.0):
+    """scale * mean((mask * (w - ab_scale * y))^2) over the image channels (fs_ruder.py:97) as a device scalar,
+    differentiable in w (the warped previous frame of ruder_stack_nhwc) and y (the styled frame, NHWC4 0..255)."""
+    return _RuderTemporalNHWC.apply(w.contiguous(), y.contiguous(), mask.detach().contiguous().float(),
+                                    float(scale), float(ab_scale))

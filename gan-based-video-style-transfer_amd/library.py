@@ -18,6 +18,8 @@ library's NHWC layout on the device.  Backward passes are themselves ``vst::`` o
   vst::temporal_sqdiff(a, b, flow, mask, scale, ab_scale, i1?, i2?)   learning-based fs_huang.py:55-56,
         fs_reconet.py:61-69 (fs_lib.warp validity, optional luminance input term)
   vst::resize_bilinear(x, out_h, out_w, mult?) F.interpolate(mode='bilinear'), fs_reconet.py:57-60
+  vst::ruder_stack(y_prev, img, flow, mask, scale)      learning-based fs_ruder.py:50-52, the recurrent input
+  vst::ruder_temporal(w, y, mask, scale, ab_scale)      fs_ruder.py:97, the temporal loss on the last frame
   vst::gram(f)                                 learning-based fast_style_transfer.py:813-817
   vst::adam_(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step)   torch.optim.Adam step
 
@@ -399,6 +401,86 @@ def _(x, out_h, out_w, mult):
     return x.new_empty((x.shape[0], x.shape[1], out_h, out_w))
 
 
+@torch.library.custom_op("vst::ruder_stack", mutates_args=())
+def ruder_stack(y_prev: Tensor, img: Tensor, flow: Tensor, mask: Tensor, scale: float) -> Tuple[Tensor, Tensor]:
+    """fs_ruder.py:50-52: (cat(img, mask, w), w) with w = fs_lib.warp(scale * y_prev, flow).  y_prev, img
+    [B,3,H,W]; flow [B,2,H,W]; mask [B,1,H,W] -> ([B,7,H,W], [B,3,H,W]).  Differentiable in y_prev."""
+    x, w = ops.ruder_stack(_nhwc(y_prev), _nhwc(img), flow.contiguous(), mask.contiguous(), scale)
+    return ops.nhwc_to_nchw(x, 7), ops.nhwc_to_nchw(w, 3)
+
+
+@ruder_stack.register_fake
+def _(y_prev, img, flow, mask, scale):
+    B, _, H, W = img.shape
+    return img.new_empty((B, 7, H, W)), img.new_empty((B, 3, H, W))
+
+
+@torch.library.custom_op("vst::ruder_stack_backward", mutates_args=())
+def ruder_stack_backward(gx: Tensor, gw: Tensor, flow: Tensor, scale: float) -> Tensor:
+    """d/dy_prev of vst::ruder_stack from both output gradients (gx [B,7,H,W], gw [B,3,H,W]) in one scatter."""
+    B, _, H, W = flow.shape
+    gy = torch.zeros((B, H, W, 4), device=flow.device, dtype=torch.float32)
+    ops.ruder_stack_bwd(_nhwc(gx), _nhwc(gw), flow.contiguous(), gy, scale)
+    return ops.nhwc_to_nchw(gy, 3)
+
+
+@ruder_stack_backward.register_fake
+def _(gx, gw, flow, scale):
+    return torch.empty_like(gw)
+
+
+def _rs_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[2])
+    ctx.scale = inputs[4]
+
+
+def _rs_bwd(ctx, gx, gw):
+    (flow,) = ctx.saved_tensors
+    return torch.ops.vst.ruder_stack_backward(gx.contiguous(), gw.contiguous(), flow, ctx.scale), None, None, None, None
+
+
+ruder_stack.register_autograd(_rs_bwd, setup_context=_rs_setup)
+
+
+@torch.library.custom_op("vst::ruder_temporal", mutates_args=())
+def ruder_temporal(w: Tensor, y: Tensor, mask: Tensor, scale: float, ab_scale: float) -> Tensor:
+    """fs_ruder.py:97: scale * mean((mask * (w - ab_scale * y))^2) over [B,3,H,W] w (the warped previous frame)
+    and y (the styled frame, 0..255); mask [B,1,H,W]."""
+    return ops.ruder_temporal(_nhwc(w), _nhwc(y), mask.contiguous(), scale, ab_scale)
+
+
+@ruder_temporal.register_fake
+def _(w, y, mask, scale, ab_scale):
+    return w.new_empty(())
+
+
+@torch.library.custom_op("vst::ruder_temporal_backward", mutates_args=())
+def ruder_temporal_backward(grad: Tensor, w: Tensor, y: Tensor, mask: Tensor, scale: float,
+                            ab_scale: float) -> Tuple[Tensor, Tensor]:
+    gw, gy = ops.ruder_temporal_bwd(_nhwc(w), _nhwc(y), mask.contiguous(), grad.contiguous(), scale, ab_scale)
+    return ops.nhwc_to_nchw(gw, 3), ops.nhwc_to_nchw(gy, 3)
+
+
+@ruder_temporal_backward.register_fake
+def _(grad, w, y, mask, scale, ab_scale):
+    return torch.empty_like(w), torch.empty_like(y)
+
+
+def _rt_setup(ctx, inputs, output):
+    w, y, mask, scale, ab_scale = inputs
+    ctx.save_for_backward(w, y, mask)
+    ctx.conf = (scale, ab_scale)
+
+
+def _rt_bwd(ctx, grad):
+    w, y, mask = ctx.saved_tensors
+    gw, gy = torch.ops.vst.ruder_temporal_backward(grad, w, y, mask, *ctx.conf)
+    return gw, gy, None, None, None
+
+
+ruder_temporal.register_autograd(_rt_bwd, setup_context=_rt_setup)
+
+
 @torch.library.custom_op("vst::gram", mutates_args=())
 def gram(f: Tensor) -> Tensor:
     """fast_style_transfer.py:813-817 gram_matrix of [B,C,H,W] features: bmm(F, F^T) / (h*w) per
@@ -454,4 +536,5 @@ def _(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
 OPS: List[str] = ["conv2d", "conv2d_backward", "conv_transpose2d", "conv_transpose2d_backward",
                   "instance_norm_act", "instance_norm_act_backward", "warp_bilinear", "warp_bilinear_backward",
                   "fbcheck", "temporal_loss", "temporal_loss_backward", "temporal_sqdiff", "temporal_sqdiff_backward",
-                  "resize_bilinear", "gram", "gram_backward", "adam_"]
+                  "resize_bilinear", "gram", "gram_backward", "adam_", "ruder_stack", "ruder_stack_backward",
+                  "ruder_temporal", "ruder_temporal_backward"]

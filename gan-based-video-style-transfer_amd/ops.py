@@ -863,6 +863,81 @@ def temporal_sqdiff_bwd(a, b, flow, mask, gout, ga, gb, scale, cl=None, ab_scale
           *args)
 
 
+def ruder_stack(y_prev, img, flow, mask, s=1.0 / 255.0, want_w=True):
+    """The Ruder net's next input (fs_ruder.py:52): x [N,H,W,8] = (img rgb, mask, fs_lib.warp(s * y_prev, flow)
+    rgb, 0) and w [N,H,W,4] = the same warped values (None unless want_w), in one pass.  y_prev: the previous
+    styled frame, NHWC4 0..255; img NHWC4 [0,1]; flow [N,2,H,W]; mask [N,1,H,W].  y_prev = flow = mask = None:
+    the blank form of fs_ruder.py:78 (channels 3..7 of x and w zero)."""
+    _dev_check(y_prev, img, flow, mask)
+    if img.dim() != 4 or img.shape[-1] != 4:
+        raise ValueError("ruder_stack: img must be NHWC4, got %s" % (tuple(img.shape),))
+    N, H, W, _ = img.shape
+    given = [t is not None for t in (y_prev, flow, mask)]
+    if any(given) != all(given):
+        raise ValueError("ruder_stack: y_prev, flow and mask are given together or not at all (the blank form)")
+    if all(given) and (y_prev.shape != img.shape or flow.shape != (N, 2, H, W) or mask.numel() != N * H * W):
+        raise ValueError("ruder_stack: y_prev %s, img %s, flow %s, mask %s do not match" %
+                         (tuple(y_prev.shape), tuple(img.shape), tuple(flow.shape), tuple(mask.shape)))
+    x = torch.empty((N, H, W, 8), device=img.device, dtype=torch.float32)
+    w = torch.empty((N, H, W, 4), device=img.device, dtype=torch.float32) if want_w else None
+    _call("vst_ruder_stack_fwd", _p(y_prev), _p(img), _p(flow), _p(mask), _p(x), _p(w), N, H, W, float(s), _stream())
+    return x, w
+
+
+def ruder_stack_bwd(gx, gw, flow, gy_prev, s=1.0 / 255.0):
+    """The one scatter of the Ruder recurrence: gy_prev (NHWC4, ACCUMULATED: zero it first) += s * scatter(valid
+    corner weights * (gx[..., 4:7] + gw)); gx [N,H,W,8] (the net's input gradient) or gw [N,H,W,4] (from the
+    temporal loss) may be None.  Deterministic mode: the combined gradient is written once and scattered in order."""
+    _dev_check(gx, gw, flow, gy_prev)
+    N, H, W, _ = gy_prev.shape
+    if gx is None and gw is None:
+        raise ValueError("ruder_stack_bwd: neither gx nor gw given")
+    if gy_prev.shape != (N, H, W, 4) or flow.shape != (N, 2, H, W) or \
+            (gx is not None and gx.shape != (N, H, W, 8)) or (gw is not None and gw.shape != (N, H, W, 4)):
+        raise ValueError("ruder_stack_bwd: gx %s, gw %s, flow %s, gy_prev %s do not match" %
+                         (None if gx is None else tuple(gx.shape), None if gw is None else tuple(gw.shape),
+                          tuple(flow.shape), tuple(gy_prev.shape)))
+    if _deterministic:
+        gbuf = torch.empty_like(gy_prev)
+        _call("vst_ruder_stack_bwd", _p(gx), _p(gw), _p(flow), None, _p(gbuf), N, H, W, float(s), _stream())
+        _warp_bwd_det(gbuf, flow, gy_prev, False, True, False, 3)
+        return gy_prev
+    _call("vst_ruder_stack_bwd", _p(gx), _p(gw), _p(flow), _p(gy_prev), None, N, H, W, float(s), _stream())
+    return gy_prev
+
+
+def _ruder_temporal_args(w, y, mask):
+    _dev_check(w, y, mask)
+    if w.dim() != 4 or w.shape[-1] != 4 or y.shape != w.shape or mask.numel() != w.numel() // 4:
+        raise ValueError("ruder_temporal: w %s, y %s, mask %s do not match (NHWC4 images, one mask plane)" %
+                         (tuple(w.shape), tuple(y.shape), tuple(mask.shape)))
+    return w.shape[:3]
+
+
+def ruder_temporal(w, y, mask, scale, ab_scale=1.0 / 255.0):
+    """scale * mean((mask * (w - s*y))^2) over the 3 image channels (fs_ruder.py:97): w the warped previous
+    frame a ruder_stack returned, y the styled frame (NHWC4, 0..255), s = ab_scale.  Device scalar."""
+    N, H, W = _ruder_temporal_args(w, y, mask)
+    loss = torch.empty((), device=w.device)
+    part = torch.empty(lib().vst_ruder_temporal_part_floats(N, H, W), device=w.device)
+    _call("vst_ruder_temporal_fwd", _p(w), _p(y), _p(mask), _p(loss), _p(part), N, H, W, float(scale),
+          float(ab_scale), _stream())
+    return loss
+
+
+def ruder_temporal_bwd(w, y, mask, gout, scale, ab_scale=1.0 / 255.0, need_w=True, need_y=True):
+    """(gw, gy) of ruder_temporal times the device scalar gout, NHWC4 with pad channel 0 (None if not needed)."""
+    N, H, W = _ruder_temporal_args(w, y, mask)
+    _dev_check(gout)
+    if not (need_w or need_y):
+        return None, None
+    gw = torch.empty_like(w) if need_w else None
+    gy = torch.empty_like(y) if need_y else None
+    _call("vst_ruder_temporal_bwd", _p(w), _p(y), _p(mask), _p(gout), _p(gw), _p(gy), N, H, W, float(scale),
+          float(ab_scale), _stream())
+    return gw, gy
+
+
 _MULT_CACHE = {}
 
 

@@ -30,6 +30,7 @@
  *   vst_warp_masked_*           methods/learning-based/fs_lib.py:5-39 warp (grid_sample * validity mask)
  *   vst_temporal_sqdiff_*       methods/learning-based/fs_huang.py:55-56, fs_reconet.py:61-69 temporal losses
  *   vst_resize_bilinear         F.interpolate(mode='bilinear') of the flow / mask planes, fs_reconet.py:57-60
+ *   vst_ruder_*                 methods/learning-based/fs_ruder.py:38-108 recurrence: input stacking, temporal loss
  *   vst_instnorm_affine_*       nn.InstanceNorm2d(affine=True) (+ReLU, + ResidualBlock layer_strength
  *                               gate) of methods/learning-based/network.py:147-298 (FastStyleNet)
  *   vst_upsample2x_*            F.interpolate(scale_factor=2) in network.py:206-207
@@ -455,6 +456,26 @@ int vst_temporal_sqdiff_bwd(const float* a, const float* b, const float* flow, c
  * sizes), times mult[c] (device, C floats; NULL = 1): the flow / mask resize of fs_reconet.py:57-60. */
 int vst_resize_bilinear(const float* x, const float* mult, float* y, int N, int C, int Hi, int Wi, int Ho,
                         int Wo, void* stream);
+/* The Ruder recurrence (fs_ruder.py:38-108): frame k is styled from cat(frame_k, mask_{k-1},
+ * warp_m(styled_{k-1} / 255, flow_{k-1})).  All images NHWC fp32; flow [N][2][H][W]; mask [N][H][W].
+ * stack_fwd: x [N][H][W][8] = (img rgb, mask, warp_m(s * y_prev, flow) rgb, 0), w [N][H][W][4] = the same warped
+ * values, pad 0 (w may be NULL).  y_prev (NHWC4, the previous styled frame, 0..255), flow and mask all NULL: the
+ * blank form of fs_ruder.py:78, channels 3..7 of x and all of w zero.
+ * stack_bwd: g = s * (gx[..., 4:7] + gw) (gx [N][H][W][8], gw NHWC4; either may be NULL).  gy_prev (NHWC4)
+ * ACCUMULATED by fp32 atomics through valid samples, and / or g WRITTEN to gbuf (NHWC4, pad 0) for the ordered
+ * scatter vst_warp_bwd_input_det(gbuf, masked = 1, negate = 0, Cl = 3); at least one of gy_prev, gbuf.
+ * temporal: loss = scale / (N*3*H*W) * sum_{c<3} (mask * (w_c - s * y_c))^2 (fs_ruder.py:97) on the w of the last
+ * stack and the last styled frame y (NHWC4, 0..255); part: vst_ruder_temporal_part_floats floats (fp64 per-block
+ * partials, fixed-order finish).  bwd: gw, gy (NHWC4, pad channel 0; either may be NULL) WRITTEN, times gout[0]. */
+int vst_ruder_stack_fwd(const float* y_prev, const float* img, const float* flow, const float* mask, float* x,
+                        float* w, int N, int H, int W, float s, void* stream);
+int vst_ruder_stack_bwd(const float* gx, const float* gw, const float* flow, float* gy_prev, float* gbuf, int N,
+                        int H, int W, float s, void* stream);
+int vst_ruder_temporal_part_floats(int N, int H, int W);
+int vst_ruder_temporal_fwd(const float* w, const float* y, const float* mask, float* loss, float* part, int N,
+                           int H, int W, float scale, float s, void* stream);
+int vst_ruder_temporal_bwd(const float* w, const float* y, const float* mask, const float* gout, float* gw,
+                           float* gy, int N, int H, int W, float scale, float s, void* stream);
 /* Affine instance norm: y = s * act(gamma[c] * xhat + beta[c]) + residual, with stats from
  * vst_instnorm_stats; s = 1 (gate NULL) or s = 2|u|/(1+|u|), u = gate_mult * gate[0] (device scalar:
  * ResidualBlock layer_strength, network.py:241-245).  residual may be NULL.  C a multiple of 4, at most 1024. */
