@@ -1131,6 +1131,31 @@ def corr_lookup(pyr, coords, B, H1, W1, H2, W2, ld0, levels, radius, cs=None):
     return out
 
 
+def altcorr_pyramid_floats(B, H, W, Dp, levels):
+    """Floats of the pooled fmap2 levels 1..levels-1 (-1 for levels outside 1..8)."""
+    return lib().vst_altcorr_pyramid_floats(B, H, W, Dp, levels)
+
+
+def altcorr_pyramid(f2, pyr, levels):
+    """Fill pyr (altcorr_pyramid_floats floats) with the 2x2 average-pooled levels of NHWC f2."""
+    _dev_check(f2, pyr)
+    B, H, W, Dp = f2.shape
+    _call("vst_altcorr_pyramid", _p(f2), _p(pyr), B, H, W, Dp, levels, _stream())
+
+
+def altcorr_lookup(f1, f2, pyr, coords, D, levels, radius, cs=None):
+    """AlternateCorrBlock window features [B, H, W, cs] from NHWC f1, f2 [B, H, W, Dp] and f2's pooled levels;
+    cs: the output channel stride (default cpad; the padded channels are written as zeros)."""
+    _dev_check(f1, f2, pyr, coords)
+    B, H, W, Dp = f1.shape
+    K = 2 * radius + 1
+    cs = cs or cpad(levels * K * K)
+    out = torch.empty((B, H, W, cs), device=f1.device)
+    _call("vst_altcorr_lookup", _p(f1), _p(f2), _p(pyr), _p(coords), _p(out), B, H, W, Dp, D, levels, radius, cs,
+          _stream())
+    return out
+
+
 # -------------------------------------------------------------------------------- StarGAN
 def concat_label_nhwc(x, label, cs=None):
     """NCHW x [N,Cx,H,W] + label [N,Cl] -> NHWC [N,H,W,cs] (StarGAN model.py:59-64)."""

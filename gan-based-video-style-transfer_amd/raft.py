@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import ops
 from .ops import cpad
-from .raft_corr import CorrBlock, coords_grid
+from .raft_corr import AlternateCorrBlock, CorrBlock, coords_grid
 
 
 ###############################################################################
@@ -196,15 +196,15 @@ class _ConvOp:
 ###############################################################################
 class RAFT(nn.Module):
     """raft.py:24-144 (full model).  ``args`` needs ``small`` (False), optionally ``mixed_precision``
-    (ignored: fp32 arithmetic), ``alternate_corr`` (False), ``dropout`` (0, inference)."""
+    (ignored: fp32 arithmetic), ``alternate_corr`` (False; True looks the correlation features up from the
+    feature maps, raft_corr.AlternateCorrBlock, instead of building the all-pairs volume), ``dropout`` (0,
+    inference)."""
 
     def __init__(self, args):
         super().__init__()
         self.args = args
         if getattr(args, "small", False):
             raise NotImplementedError("RAFT small model (SmallEncoder / SmallUpdateBlock) is not ported")
-        if getattr(args, "alternate_corr", False):
-            raise NotImplementedError("alternate_corr (the CUDA sampler extension) is not ported")
         self.hidden_dim = hdim = 128
         self.context_dim = cdim = 128
         args.corr_levels = 4
@@ -319,8 +319,12 @@ class RAFT(nn.Module):
         if Hp % 8 or Wp % 8:
             raise ValueError("RAFT: padded image size must be divisible by 8 (use InputPadder)")
         fmaps = self._encode(P["fnet"], "instance", imgs)
-        corr_fn = CorrBlock.from_nhwc(fmaps[:B], fmaps[B:], 256, self.args.corr_levels, self.args.corr_radius,
-                                      role=role)
+        if getattr(self.args, "alternate_corr", False):  # raft.py:104-105: no all-pairs volume
+            corr_fn = AlternateCorrBlock.from_nhwc(fmaps[:B], fmaps[B:], 256, self.args.corr_levels,
+                                                   self.args.corr_radius)
+        else:
+            corr_fn = CorrBlock.from_nhwc(fmaps[:B], fmaps[B:], 256, self.args.corr_levels, self.args.corr_radius,
+                                          role=role)
         cnet = self._encode(P["cnet"], "batch", imgs[:B])
         h8, w8 = cnet.shape[1], cnet.shape[2]
         dev = cnet.device
@@ -398,8 +402,9 @@ def compute_raft(model, img1, img2, it=20):
     return flow_up
 
 
-def raft_flops(B, H, W, iters):
-    """Algorithmic conv + corr FLOPs of one RAFT call at padded size HxW (for throughput reporting)."""
+def raft_flops(B, H, W, iters, alternate_corr=False):
+    """Algorithmic conv + corr FLOPs of one RAFT call at padded size HxW (for throughput reporting);
+    alternate_corr: the per-iteration window dot products, iters*B*HW*L*(2r+2)^2*D*2, replace the all-pairs GEMM."""
     h, w = H // 8, W // 8
     P8 = B * h * w
 
@@ -414,6 +419,8 @@ def raft_flops(B, H, W, iters):
         enc += conv(nimg * h * w, 96, 128, 9) + 3 * conv(nimg * h * w, 128, 128, 9) + conv(nimg * h * w, 96, 128, 1)
         enc += conv(nimg * h * w, 128, out, 1)
     corr = 2.0 * B * (h * w) ** 2 * 256
+    if alternate_corr:
+        corr = iters * B * h * w * 4 * (2 * 4 + 2) ** 2 * 256 * 2.0
     upd = (conv(P8, 324, 256, 1) + conv(P8, 256, 192, 9) + conv(P8, 2, 128, 49) + conv(P8, 128, 64, 9)
            + conv(P8, 256, 126, 9) + 2 * (conv(P8, 384, 256, 5) + conv(P8, 384, 128, 5))
            + conv(P8, 128, 256, 9) + conv(P8, 256, 2, 9))

@@ -13,7 +13,9 @@ MI355X design:
   * levels 1..L-1 are 2x2 average pools of the previous level (one streaming kernel per level,
     ATen's summation order), packed after level 0;
   * the (2r+1)^2 window lookup per level is one gather kernel writing NHWC; the NCHW
-    [B, L*(2r+1)^2, H1, W1] result of the reference is produced by the layout kernel.
+    [B, L*(2r+1)^2, H1, W1] result of the reference is produced by the layout kernel;
+  * AlternateCorrBlock (corr.py:63-91) gives the same features without the volume: fmap2 is pooled instead
+    (a few MB), and each lookup forms the (2r+2)^2 dot products per (pixel, level) on the fly (csrc/altcorr.hip).
 """
 import torch
 
@@ -92,6 +94,64 @@ class CorrBlock:
         """corr.py:53-60: [B, H, W, 1, H, W] all-pairs volume / sqrt(D)."""
         cb = CorrBlock(fmap1, fmap2, num_levels=1, radius=0)
         return cb.level(0).reshape(cb.B, cb.H, cb.W, 1, cb.H, cb.W)
+
+
+class AlternateCorrBlock:
+    """utils/raft/raft/corr.py:63-91 ``AlternateCorrBlock(fmap1, fmap2, num_levels=4, radius=4)``: CorrBlock's
+    window features computed from the feature maps at every lookup, without the B*(HW)^2 volume.
+
+    Pooling the volume over (h2, w2) equals correlating with a pooled fmap2, and interpolating correlations
+    equals interpolating dot products, so ``__call__`` returns what CorrBlock's does up to fp32 rounding.
+    Keeps references to the two NHWC maps and owns only fmap2's pooled levels 1..L-1 (the reference pools
+    both maps num_levels times and never reads the extras; here fmap2 only, num_levels - 1 times)."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        B, D, H, W = fmap1.shape
+        if tuple(fmap2.shape) != (B, D, H, W):
+            raise ValueError("AlternateCorrBlock: fmap1 and fmap2 must have the same shape")
+        self._check_levels(H, W, num_levels)
+        Dp = cpad(D)
+        self._build(ops.nchw_to_nhwc(fmap1.float().contiguous(), Dp), ops.nchw_to_nhwc(fmap2.float().contiguous(), Dp),
+                    D, num_levels, radius)
+
+    @classmethod
+    def from_nhwc(cls, f1, f2, D, num_levels=4, radius=4):
+        """Build from NHWC feature maps [B, H, W, cpad(D)] (RAFT's fnet output, no layout pass); channels
+        D.. of both maps must be zero."""
+        if tuple(f1.shape) != tuple(f2.shape):
+            raise ValueError("AlternateCorrBlock: fmap1 and fmap2 must have the same shape")
+        cls._check_levels(f1.shape[1], f1.shape[2], num_levels)
+        self = cls.__new__(cls)
+        self._build(f1.contiguous(), f2.contiguous(), D, num_levels, radius)
+        return self
+
+    @staticmethod
+    def _check_levels(H, W, num_levels):
+        if num_levels > 1 and ((H >> (num_levels - 1)) < 2 or (W >> (num_levels - 1)) < 2):
+            raise ValueError("AlternateCorrBlock: the coarsest level must be at least 2x2")
+
+    def _build(self, f1, f2, D, num_levels, radius):
+        self.num_levels, self.radius = num_levels, radius
+        B, H, W, Dp = f1.shape
+        self.B, self.H, self.W, self.D = B, H, W, D
+        self.f1, self.f2 = f1, f2
+        n = ops.altcorr_pyramid_floats(B, H, W, Dp, num_levels)
+        if n < 0:
+            raise ValueError("AlternateCorrBlock: num_levels must be in 1..8")
+        self.pyr = torch.empty(n, device=f1.device)
+        ops.altcorr_pyramid(f2, self.pyr, num_levels)
+
+    def lookup_nhwc(self, coords, cs=None):
+        """[B, H, W, cs or cpad(L*(2r+1)^2)] window features at coords [B, 2, H, W] (x, y pixels); the channels
+        past L*(2r+1)^2 are zero."""
+        if tuple(coords.shape) != (self.B, 2, self.H, self.W):
+            raise ValueError("AlternateCorrBlock: coords must be [B, 2, H, W] of the feature maps")
+        return ops.altcorr_lookup(self.f1, self.f2, self.pyr, coords.float().contiguous(), self.D, self.num_levels,
+                                  self.radius, cs=cs)
+
+    def __call__(self, coords):
+        K = 2 * self.radius + 1
+        return ops.nhwc_to_nchw(self.lookup_nhwc(coords), self.num_levels * K * K)
 
 
 def coords_grid(batch, ht, wd, device="cuda"):

@@ -532,6 +532,22 @@ int vst_corr_pyramid(float* pyr, long P, int H2, int W2, long ld0, int levels, v
  * samples x + (a - r), y + (c - r) at level lvl (align_corners=True bilinear, zeros outside). */
 int vst_corr_lookup(const float* pyr, const float* coords, float* out, int B, int H1, int W1, int H2,
                     int W2, long ld0, int levels, int radius, int Cs, void* stream);
+/* AlternateCorrBlock (utils/raft/raft/corr.py:63-91): the same window features computed from the two
+ * feature maps, without the all-pairs volume.  f1, f2: NHWC [B][H][W][Dp] (Dp % 4 == 0, D <= Dp logical
+ * channels, the padded ones zero in both maps).  pyr holds avg_pool2d(f2, 2, 2) (floor) levels
+ * 1..levels-1, [B][H>>l][W>>l][Dp] each, packed; level 0 is f2 itself and is not copied
+ * (vst_altcorr_pyramid_floats: the buffer's floats, -1 unless 1 <= levels <= 8; pyr may be NULL for
+ * levels == 1).  vst_altcorr_lookup writes out[b][h][w][c] (NHWC, Cs >= levels*(2r+1)^2, extra channels
+ * 0) with vst_corr_lookup's channel order: channel lvl*(2r+1)^2 + a*(2r+1) + c is
+ * <f1[b,h,w,:], bilinear(level lvl of f2, x/2^lvl + (a - r), y/2^lvl + (c - r))> / sqrt(D)
+ * (align_corners=True, zeros outside the level), formed from the (2r+2)^2 integer-position dot products
+ * at floor(coords/2^lvl) + (-r .. r+1) that share the pixel's fractional offset.  fp32 FMA whatever the
+ * conv math mode, no atomics, no allocation, no host synchronisation; radius <= 7; every level at least
+ * 2x2. */
+long vst_altcorr_pyramid_floats(int B, int H, int W, int Dp, int levels);
+int vst_altcorr_pyramid(const float* f2, float* pyr, int B, int H, int W, int Dp, int levels, void* stream);
+int vst_altcorr_lookup(const float* f1, const float* f2, const float* pyr, const float* coords, float* out,
+                       int B, int H, int W, int Dp, int D, int levels, int radius, int Cs, void* stream);
 
 /* ---- StarGAN -------------------------------------------------------------- */
 /* methods/GAN-based/StarGAN/model.py:59-64: y = NHWC(cat([x, label replicated], 1)), x NCHW
