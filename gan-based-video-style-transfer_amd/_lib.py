@@ -128,6 +128,9 @@ SIGNATURES = {
     "vst_instnorm_affine_fwd": (I, [P, P, P, P, P, F, P, P, I, I, I, I, F, P]),
     "vst_instnorm_affine_ws_bytes": (SZ, [I, I, I]),
     "vst_instnorm_affine_bwd": (I, [P, P, P, P, P, P, F, P, P, P, P, P, P, I, I, I, I, F, I, P]),
+    "vst_cond_instnorm_ws_bytes": (SZ, [I, I, I]),
+    "vst_cond_instnorm_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "vst_cond_instnorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "vst_upsample2x_fwd": (I, [P, P, I, I, I, I, P]),
     "vst_upsample2x_bwd": (I, [P, P, I, I, I, I, P]),
     "vst_scaled_tanh_fwd": (I, [P, P, L, I, I, P]),

@@ -722,6 +722,196 @@ __global__ void in_aff_bwd_apply_k(const float4* __restrict__ gy, const float4* 
 }
 
 
+// ---- conditional InstanceNorm (ConditionalBatchNorm2d, learning-based network.py:120-145) -------
+// y = act(ge * (w * xhat + b) + be) with {ge, be} = the halves of embedding row sid[n], {w, b} the inner
+// InstanceNorm2d(affine=True); folded per (n, c) into the affine kernels' form z = x * al + sh:
+//   A = ge * w, B = ge * b + be, al = rstd * A, sh = B - mean * al      (A = B = 0 for pad channels c >= Cl)
+// sid is device memory and is clamped to [0, S) here, so no value of it reads outside the table.
+__device__ __forceinline__ int cond_row(const int* __restrict__ sid, int n, int S) {
+  const int s = sid[n];
+  return s < 0 ? 0 : (s >= S ? S - 1 : s);
+}
+
+__device__ __forceinline__ float2 cond_alsh(const float* __restrict__ stats, const int* __restrict__ sid,
+                                            const float* __restrict__ embed, const float* __restrict__ bnw,
+                                            const float* __restrict__ bnb, int n, int c, int C, int Cl, int S) {
+  if (c >= Cl) return make_float2(0.f, 0.f);
+  const float* row = embed + (long)cond_row(sid, n, S) * 2 * Cl;
+  const float ge = row[c], be = row[Cl + c];
+  const float A = ge * bnw[c], B = ge * bnb[c] + be;
+  const float mean = stats[2 * ((long)n * C + c)], rstd = stats[2 * ((long)n * C + c) + 1];
+  const float al = rstd * A;
+  return make_float2(al, B - mean * al);
+}
+
+// tab[n*C + c] = {al, sh}: the forward apply's coefficients, one thread per (n, c)
+__global__ void cond_coef_k(const float* __restrict__ stats, const int* __restrict__ sid,
+                            const float* __restrict__ embed, const float* __restrict__ bnw,
+                            const float* __restrict__ bnb, float2* __restrict__ tab, int N, int C, int Cl, int S) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * C) return;
+  tab[i] = cond_alsh(stats, sid, embed, bnw, bnb, i / C, i % C, C, Cl, S);
+}
+
+__global__ void cond_apply_k(const float4* __restrict__ x, const float4* __restrict__ tab, float4* __restrict__ y,
+                             long total4, int HW, int C4, int act) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total4) return;
+  const int c4 = i % C4;
+  const int n = (i / C4) / HW;
+  const float4* t = tab + ((long)n * C4 + c4) * 2;
+  const float4 t0 = t[0], t1 = t[1], v = x[i];  // {al0, sh0, al1, sh1}, {al2, sh2, al3, sh3}
+  y[i] = make_float4(apply_act(v.x * t0.x + t0.y, act, 0.f), apply_act(v.y * t0.z + t0.w, act, 0.f),
+                     apply_act(v.z * t1.x + t1.y, act, 0.f), apply_act(v.w * t1.z + t1.w, act, 0.f));
+}
+
+// backward partials per (n, c) slice: {sum gz, sum gz*xhat, sum xhat}, gz = gy * act'(z).  Each thread gathers
+// its four channels' coefficients once, ahead of its pixel rows.
+__global__ __launch_bounds__(NRED) void cond_partial_k(const float* __restrict__ x, const float* __restrict__ gy,
+                                                       const float* __restrict__ stats, const int* __restrict__ sid,
+                                                       const float* __restrict__ embed,
+                                                       const float* __restrict__ bnw, const float* __restrict__ bnb,
+                                                       double* __restrict__ part, int HW, int C, int Cl, int S,
+                                                       int LP, int PG, int SP, int nsplit, int act) {
+  constexpr int NV = 3;
+  __shared__ double red[NV * 4][NRED];
+  const int t = threadIdx.x, c4 = t % LP, pg = t / LP;
+  const int n = blockIdx.y, z = blockIdx.x;
+  const int p0 = z * SP, p1 = min(HW, p0 + SP);
+  double acc[NV][4];
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[v][j] = 0.0;
+  float mean[4], rstd[4], al[4], sh[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = 4 * c4 + j;
+    mean[j] = stats[2 * ((long)n * C + c)];
+    rstd[j] = stats[2 * ((long)n * C + c) + 1];
+    const float2 k = cond_alsh(stats, sid, embed, bnw, bnb, n, c, C, Cl, S);
+    al[j] = k.x;
+    sh[j] = k.y;
+  }
+  const float4* xb = reinterpret_cast<const float4*>(x) + (long)n * HW * LP + c4;
+  const float4* gb = reinterpret_cast<const float4*>(gy) + (long)n * HW * LP + c4;
+  for (int p = p0 + pg; pg < PG && p < p1; p += PG) {
+    const float4 v = xb[(long)p * LP];
+    const float4 gv = gb[(long)p * LP];
+    const float xv[4] = {v.x, v.y, v.z, v.w};
+    const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float xh = (xv[j] - mean[j]) * rstd[j];
+      const float zz = xv[j] * al[j] + sh[j];
+      const float g = (act == VST_ACT_RELU && !(zz > 0.f)) ? 0.f : gg[j];
+      acc[0][j] += g;
+      acc[1][j] += (double)g * xh;
+      acc[2][j] += xh;
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[v * 4 + j][t] = acc[v][j];
+  __syncthreads();
+  if (pg == 0) {
+    double* dst = part + (((long)n * nsplit + z) * C + 4 * c4) * NV;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        double s = 0.0;
+        for (int q = 0; q < PG; ++q) s += red[v * 4 + j][q * LP + c4];
+        dst[j * NV + v] = s;
+      }
+  }
+}
+
+// tab[n*C+c] = {al, sh}, coef[n*C+c] = {mean gz, mean gz*xhat} for the backward apply;
+// sums[n*C+c] = {sum gz, sum gz*xhat, dbias term}
+__global__ void cond_finalize_k(const double* __restrict__ part, const float* __restrict__ stats,
+                                const int* __restrict__ sid, const float* __restrict__ embed,
+                                const float* __restrict__ bnw, const float* __restrict__ bnb,
+                                float2* __restrict__ tab, float2* __restrict__ coef, double* __restrict__ sums,
+                                int N, int HW, int C, int Cl, int S, int nsplit) {
+  double a[3];
+  const int n = blockIdx.y;
+  if (!fold_slices<3>(part, n, C, nsplit, a)) return;
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int idx = n * C + c;
+  const float2 k = cond_alsh(stats, sid, embed, bnw, bnb, n, c, C, Cl, S);
+  const double mg = a[0] / HW, mgx = a[1] / HW;
+  tab[idx] = k;
+  coef[idx] = make_float2((float)mg, (float)mgx);
+  sums[3 * idx + 0] = a[0];
+  sums[3 * idx + 1] = a[1];
+  sums[3 * idx + 2] = (double)k.x * ((a[0] - HW * mg) - mgx * a[2]);
+}
+
+// one block, a thread per real channel: the table rows style by style (samples in index order, every row
+// written, zeros for a style no sample carries), then the inner norm's weight / bias and the conv bias
+__global__ void cond_param_grad_k(const double* __restrict__ sums, const int* __restrict__ sid,
+                                  const float* __restrict__ embed, const float* __restrict__ bnw,
+                                  const float* __restrict__ bnb, float* __restrict__ dembed,
+                                  float* __restrict__ dbnw, float* __restrict__ dbnb, float* __restrict__ dbias,
+                                  int N, int C, int Cl, int S, int accumulate) {
+  for (int c = threadIdx.x; c < Cl; c += blockDim.x) {
+    const double w = bnw[c], b = bnb[c];
+    if (dembed)
+      for (int s = 0; s < S; ++s) {
+        double dg = 0.0, db = 0.0;
+        for (int n = 0; n < N; ++n) {
+          if (cond_row(sid, n, S) != s) continue;
+          const double* q = sums + 3 * ((long)n * C + c);
+          dg += w * q[1] + b * q[0];
+          db += q[0];
+        }
+        float* row = dembed + (long)s * 2 * Cl;
+        row[c] = accumulate ? row[c] + (float)dg : (float)dg;
+        row[Cl + c] = accumulate ? row[Cl + c] + (float)db : (float)db;
+      }
+    double dw = 0.0, dbb = 0.0, sb = 0.0;
+    for (int n = 0; n < N; ++n) {
+      const double* q = sums + 3 * ((long)n * C + c);
+      const double ge = embed[(long)cond_row(sid, n, S) * 2 * Cl + c];
+      dw += ge * q[1];
+      dbb += ge * q[0];
+      sb += q[2];
+    }
+    if (dbnw) dbnw[c] = accumulate ? dbnw[c] + (float)dw : (float)dw;
+    if (dbnb) dbnb[c] = accumulate ? dbnb[c] + (float)dbb : (float)dbb;
+    if (dbias) dbias[c] = accumulate ? dbias[c] + (float)sb : (float)sb;
+  }
+}
+
+__global__ void cond_bwd_apply_k(const float4* __restrict__ gy, const float4* __restrict__ x,
+                                 const float4* __restrict__ stats, const float4* __restrict__ tab,
+                                 const float4* __restrict__ coef, float4* __restrict__ dx, long total4, int HW,
+                                 int C4, int act) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total4) return;
+  const int c4 = i % C4;
+  const int n = (i / C4) / HW;
+  const long q = ((long)n * C4 + c4) * 2;
+  const float4 g4 = gy[i], v = x[i];
+  const float4 s0 = stats[q], s1 = stats[q + 1], t0 = tab[q], t1 = tab[q + 1], k0 = coef[q], k1 = coef[q + 1];
+  const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, xv[4] = {v.x, v.y, v.z, v.w};
+  const float mean[4] = {s0.x, s0.z, s1.x, s1.z}, rstd[4] = {s0.y, s0.w, s1.y, s1.w};
+  const float al[4] = {t0.x, t0.z, t1.x, t1.z}, sh[4] = {t0.y, t0.w, t1.y, t1.w};
+  const float kg[4] = {k0.x, k0.z, k1.x, k1.z}, kx[4] = {k0.y, k0.w, k1.y, k1.w};
+  float o[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float zz = xv[j] * al[j] + sh[j];
+    const float g = (act == VST_ACT_RELU && !(zz > 0.f)) ? 0.f : gg[j];
+    const float xh = (xv[j] - mean[j]) * rstd[j];
+    o[j] = al[j] * (g - kg[j] - xh * kx[j]);
+  }
+  dx[i] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+
 // ---- running statistics (nn.InstanceNorm2d(track_running_stats=True), StarGAN model.py:13-16) ---
 // ATen instance_norm: batch_norm over (1, N*C, HW) with the running buffers repeated N times, then
 // the N copies averaged: rm = (1-m) rm + m * mean_n(mean_nc); rv = (1-m) rv + m * mean_n(var_nc *
@@ -1038,6 +1228,65 @@ extern "C" int vst_instnorm_affine_bwd(const float* gy, const float* x, const fl
                      beta, gate, gate_mult, coef, reinterpret_cast<float4*>(dx), total4, HW, C / 4, act,
                      slope);
   return check_launch("instnorm_affine_bwd");
+}
+
+// workspace: slice partials [N][nsplit][C][3] fp64, then the {al, sh} and {mean gz, mean gz*xhat} tables
+// (float2 [N][C] each), then the folded sums [N][C][3] fp64.  The forward uses the first N*C float2 only.
+extern "C" size_t vst_cond_instnorm_ws_bytes(int N, int HW, int C) {
+  RedGeom g;
+  if (N <= 0 || HW <= 0 || !red_geom(N, HW, C, g)) return 0;
+  return (size_t)N * g.nsplit * C * 3 * sizeof(double) + (size_t)N * C * (2 * sizeof(float2) + 3 * sizeof(double)) +
+         256;
+}
+
+static bool cond_args_ok(int N, int HW, int C, int Cl, int S, int act, RedGeom& g) {
+  return N > 0 && HW > 0 && red_geom(N, HW, C, g) && Cl > 0 && Cl <= C && S >= 1 &&
+         (act == VST_ACT_NONE || act == VST_ACT_RELU);
+}
+
+extern "C" int vst_cond_instnorm_fwd(const float* x, const float* stats, const int* sid, const float* embed,
+                                     const float* bn_weight, const float* bn_bias, float* y, float* ws, int N,
+                                     int HW, int C, int Cl, int S, int act, void* stream) {
+  RedGeom g;
+  VST_REQUIRE(x && stats && sid && embed && bn_weight && bn_bias && y && ws && cond_args_ok(N, HW, C, Cl, S, act, g),
+              "cond_instnorm_fwd: bad args (C a multiple of 4, at most 1024; 0 < Cl <= C; S >= 1; act none | relu)");
+  hipStream_t s = (hipStream_t)stream;
+  float2* tab = reinterpret_cast<float2*>(ws);
+  hipLaunchKernelGGL(cond_coef_k, dim3(ceil_div((long)N * C, 256)), dim3(256), 0, s, stats, sid, embed, bn_weight,
+                     bn_bias, tab, N, C, Cl, S);
+  const long total4 = (long)N * HW * C / 4;
+  hipLaunchKernelGGL(cond_apply_k, dim3(ceil_div(total4, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(x),
+                     reinterpret_cast<const float4*>(tab), reinterpret_cast<float4*>(y), total4, HW, C / 4, act);
+  return check_launch("cond_instnorm_fwd");
+}
+
+extern "C" int vst_cond_instnorm_bwd(const float* gy, const float* x, const float* stats, const int* sid,
+                                     const float* embed, const float* bn_weight, const float* bn_bias, float* dx,
+                                     float* dembed, float* dbn_weight, float* dbn_bias, float* dbias, float* ws,
+                                     int N, int HW, int C, int Cl, int S, int act, int accumulate, void* stream) {
+  RedGeom g;
+  VST_REQUIRE(gy && x && stats && sid && embed && bn_weight && bn_bias && dx && ws &&
+                  cond_args_ok(N, HW, C, Cl, S, act, g),
+              "cond_instnorm_bwd: bad args (C a multiple of 4, at most 1024; 0 < Cl <= C; S >= 1; act none | relu)");
+  hipStream_t s = (hipStream_t)stream;
+  double* part = reinterpret_cast<double*>(ws);
+  char* p = reinterpret_cast<char*>(ws) + (size_t)N * g.nsplit * C * 3 * sizeof(double);
+  float2* tab = reinterpret_cast<float2*>(p);
+  float2* coef = tab + (size_t)N * C;
+  double* sums = reinterpret_cast<double*>(coef + (size_t)N * C);
+  hipLaunchKernelGGL(cond_partial_k, dim3(g.nsplit, N), dim3(NRED), 0, s, x, gy, stats, sid, embed, bn_weight,
+                     bn_bias, part, HW, C, Cl, S, g.LP, g.PG, g.SP, g.nsplit, act);
+  hipLaunchKernelGGL(cond_finalize_k, dim3(ceil_div(C, 64), N), dim3(256), 0, s, part, stats, sid, embed,
+                     bn_weight, bn_bias, tab, coef, sums, N, HW, C, Cl, S, g.nsplit);
+  if (dembed || dbn_weight || dbn_bias || dbias)
+    hipLaunchKernelGGL(cond_param_grad_k, dim3(1), dim3(256), 0, s, sums, sid, embed, bn_weight, bn_bias, dembed,
+                       dbn_weight, dbn_bias, dbias, N, C, Cl, S, accumulate);
+  const long total4 = (long)N * HW * C / 4;
+  hipLaunchKernelGGL(cond_bwd_apply_k, dim3(ceil_div(total4, 256)), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(x),
+                     reinterpret_cast<const float4*>(stats), reinterpret_cast<const float4*>(tab),
+                     reinterpret_cast<const float4*>(coef), reinterpret_cast<float4*>(dx), total4, HW, C / 4, act);
+  return check_launch("cond_instnorm_bwd");
 }
 
 extern "C" int vst_instnorm_running_update(const float* stats, float* running_mean, float* running_var,

@@ -14,8 +14,11 @@ MI355X design: the whole net is one autograd node over NHWC fp32 tensors —
     the same backward pass);
   * nearest 2x upsampling materialised by a streaming kernel (its backward sums 2x2 blocks);
   * ConvTanh's tanh(x/255)*150+127.5 as a streaming epilogue kernel.
-Only ``n_styles == 1`` (plain InstanceNorm2d(affine=True)) is on the HIP path; the conditional
-(embedding) norm of multi-style models raises NotImplementedError.
+``FastStyleNet`` is the single-style net (``n_styles == 1``, plain InstanceNorm2d(affine=True)).  The
+reference's multi-style ``FastStyleNet(num_inp, n_styles > 1)`` is ``MultiStyleNet``: conv1..3 and
+deconv1..2 carry the conditional norm (an embedding row per style scaling and shifting the affine
+InstanceNorm, network.py:120-145), applied by the vst_cond_instnorm_* kernels from device-resident
+style ids; ``make_net`` picks between the two, ``Dumoulin`` is its train step (fs_dumoulin.py).
 """
 import torch
 import torch.nn as nn
@@ -71,15 +74,43 @@ class ConvTanh(ConvLayer):
         self.tanh = _Marker("Tanh")
 
 
+class _Embedding(nn.Module):
+    """Parameter holder with nn.Embedding's state: weight [num_embeddings, embedding_dim]."""
+
+    def __init__(self, n, dim):
+        super().__init__()
+        self.num_embeddings, self.embedding_dim = n, dim
+        self.weight = nn.Parameter(torch.zeros(n, dim))
+
+    def extra_repr(self):
+        return f"{self.num_embeddings}, {self.embedding_dim}"
+
+
+class ConditionalInstanceNorm(nn.Module):
+    """network.py:120-145 ConditionalBatchNorm2d(C, S): parameter holder with children ``bn``
+    (InstanceNorm2d(affine=True): weight 1, bias 0) and ``embed`` (Embedding(S, 2C): the scale half N(1, 0.02),
+    the shift half 0).  Applied by vst_cond_instnorm_* (ops.cond_instnorm_fwd / _bwd)."""
+
+    def __init__(self, c, n_styles):
+        super().__init__()
+        self.num_features, self.n_styles = c, n_styles
+        self.bn = InstanceNormAffine(c)
+        self.embed = _Embedding(n_styles, 2 * c)
+        with torch.no_grad():
+            self.embed.weight[:, :c].normal_(1, 0.02)
+
+
+def _style_norm(cout, n_styles):
+    return InstanceNormAffine(cout) if n_styles == 1 else ConditionalInstanceNorm(cout, n_styles)
+
+
 class ConvInstRelu(ConvLayer):
-    """network.py:146-170 (n_styles == 1)."""
+    """network.py:146-170."""
 
     def __init__(self, cin, cout, kernel_size, stride, n_styles=1):
         super().__init__(cin, cout, kernel_size, stride)
-        if n_styles != 1:
-            raise NotImplementedError("conditional instance norm (n_styles > 1) is not on the HIP path")
         self.n_styles = n_styles
-        self.instance = InstanceNormAffine(cout)
+        self.instance = _style_norm(cout, n_styles)
         self.relu = _Marker("ReLU")
 
 
@@ -89,15 +120,13 @@ class UpsampleConvInstRelu(nn.Module):
     def __init__(self, cin, cout, kernel_size, stride, upsample=None, n_styles=1):
         super().__init__()
         k = kernel_size
-        if n_styles != 1:
-            raise NotImplementedError("conditional instance norm (n_styles > 1) is not on the HIP path")
         if upsample not in (None, 2) or stride != 1:
             raise NotImplementedError("UpsampleConvInstRelu: upsample 2 / stride 1 only on the HIP path")
         self.upsample = upsample
         self.reflection_pad = _Marker("ReflectionPad2d(%d)" % (k // 2))
         self.conv2d = Conv2d(cin, cout, k, stride=stride)
         self.n_styles = n_styles
-        self.instance = InstanceNormAffine(cout)
+        self.instance = _style_norm(cout, n_styles)
         self.relu = _Marker("ReLU")
         self.k, self.stride = k, stride
 
@@ -121,8 +150,14 @@ class FastStyleNet(FlatNet):
     x is the [0, 1] image (3 channels, or 7 for Ruder's stacked input: frame, mask, warped previous frame)."""
 
     def __init__(self, num_inp, n_styles=1):
-        super().__init__()
-        self.input_nc, self.output_nc = num_inp, 3
+        if n_styles != 1:
+            raise NotImplementedError("FastStyleNet is the single-style net (plain InstanceNorm2d(affine=True)); "
+                                      "MultiStyleNet(num_inp, n_styles) / make_net carry the conditional norm")
+        self._build(num_inp, 1)
+
+    def _build(self, num_inp, n_styles):
+        FlatNet.__init__(self)
+        self.input_nc, self.output_nc, self.n_styles = num_inp, 3, n_styles
         self.conv1 = ConvInstRelu(num_inp, 32, kernel_size=9, stride=1, n_styles=n_styles)
         self.conv2 = ConvInstRelu(32, 64, kernel_size=3, stride=2, n_styles=n_styles)
         self.conv3 = ConvInstRelu(64, 128, kernel_size=3, stride=2, n_styles=n_styles)
@@ -171,20 +206,90 @@ class FastStyleNet(FlatNet):
         return P
 
     def forward_nhwc(self, x, style_strength=1.0):
-        return _FastStyleFn.apply(x, self._anchor(), self, float(style_strength))
+        return _FastStyleFn.apply(x, self._anchor(), self, float(style_strength), _AFFINE_NORM)
 
     def forward(self, x, style_strength=1.0, s_id=0):
         feats, img = self.forward_nhwc(_ToNHWC.apply(x, cpad(self.input_nc)), style_strength)
         return _ToNCHW.apply(feats, 128), _ToNCHW.apply(img, 3)
 
 
+class MultiStyleNet(FastStyleNet):
+    """network.py:263-298 with n_styles > 1: FastStyleNet(num_inp, n_styles) whose conv1..3 / deconv1..2 norms are
+    ConditionalInstanceNorm (the ResidualBlocks keep plain InstanceNorm2d(affine=True), network.py:224-236); same
+    module tree and state_dict keys (``*.instance.bn.*``, ``*.instance.embed.weight``), SelectiveLoadModule
+    loading; 1,679,240 + 640 * n_styles parameters for num_inp = 3.
+
+    forward(x, style_strength=1.0, s_id=0) -> (features, image).  s_id: a Python int or a 0-dim tensor (long or
+    float, truncated as ``.long()`` does) — the reference's one style for the whole batch — or, beyond what the
+    reference can express, a length-N sequence / 1-D tensor with one style per sample: sample n is then computed
+    as if run alone with the scalar id s_id[n].  Ids given as host values are range-checked (ValueError); a
+    device tensor is never copied back, the kernels clamp it to [0, n_styles)."""
+
+    def __init__(self, num_inp, n_styles):
+        if int(n_styles) < 2:
+            raise ValueError("MultiStyleNet: n_styles >= 2 (FastStyleNet is the single-style net; see make_net)")
+        self._build(num_inp, int(n_styles))
+
+    def forward_nhwc(self, x, style_strength=1.0, s_id=0):
+        sid = ops.style_ids(s_id, x.shape[0], self.n_styles, x.device)
+        return _FastStyleFn.apply(x, self._anchor(), self, float(style_strength), _CondNorm(sid))
+
+    def forward(self, x, style_strength=1.0, s_id=0):
+        feats, img = self.forward_nhwc(_ToNHWC.apply(x, cpad(self.input_nc)), style_strength, s_id)
+        return _ToNCHW.apply(feats, 128), _ToNCHW.apply(img, 3)
+
+
+def make_net(num_inp, n_styles=1):
+    """The reference's ``FastStyleNet(num_inp, n_styles)`` constructor: FastStyleNet for one style, MultiStyleNet
+    otherwise (the name INTEGRATION.md binds in reference code)."""
+    return FastStyleNet(num_inp, 1) if int(n_styles) == 1 else MultiStyleNet(num_inp, n_styles)
+
+
 def _aff(mod):
     return mod.weight.detach(), mod.bias.detach()
 
 
+class _AffineNorm:
+    """The norm + ReLU step of conv1..3 / deconv1..2 and its backward, as _FastStyleFn takes it: plain
+    InstanceNorm2d(affine=True) (FastStyleNet)."""
+
+    def fwd(self, y, s, inst):
+        g, b = _aff(inst)
+        return ops.instnorm_affine_fwd(y, s, g, b, "relu")
+
+    def bwd(self, g, y, s, inst, conv_mod, train_w):
+        gam, bet = _aff(inst)
+        kw = dict(dgamma=inst.weight.grad, dbeta=inst.bias.grad, dbias=conv_mod.bias.grad) if train_w else {}
+        return ops.instnorm_affine_bwd(g, y, s, gam, bet, "relu", accumulate=True, **kw)
+
+
+class _CondNorm:
+    """... the conditional norm of MultiStyleNet: ``sid`` is the batch's device int32 style ids (ops.style_ids)."""
+
+    def __init__(self, sid):
+        self.sid = sid
+
+    @staticmethod
+    def _params(inst):
+        return inst.embed.weight.detach(), inst.bn.weight.detach(), inst.bn.bias.detach()
+
+    def fwd(self, y, s, inst):
+        return ops.cond_instnorm_fwd(y, s, self.sid, *self._params(inst), "relu")
+
+    def bwd(self, g, y, s, inst, conv_mod, train_w):
+        kw = {}
+        if train_w:
+            kw = dict(dembed=inst.embed.weight.grad, dbn_w=inst.bn.weight.grad, dbn_b=inst.bn.bias.grad,
+                      dbias=conv_mod.bias.grad)
+        return ops.cond_instnorm_bwd(g, y, s, self.sid, *self._params(inst), "relu", accumulate=True, **kw)
+
+
+_AFFINE_NORM = _AffineNorm()
+
+
 class _FastStyleFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, net, strength):
+    def forward(ctx, x, anchor, net, strength, norm):
         ctx.set_materialize_grads(False)
         P = net.packs()
         role = "fwd" if any(ctx.needs_input_grad[:2]) else "infer"
@@ -197,8 +302,7 @@ class _FastStyleFn(torch.autograd.Function):
         def cir(inp, layer, key, cout, k, st):
             y = conv(inp, key, cout, k, st)
             s = ops.instnorm_stats(y)
-            g, b = _aff(layer.instance)
-            return y, s, ops.instnorm_affine_fwd(y, s, g, b, "relu")
+            return y, s, norm.fwd(y, s, layer.instance)
 
         a = x
         for name, cout, k, st in (("conv1", 32, 9, 1), ("conv2", 64, 3, 2), ("conv3", 128, 3, 2)):
@@ -232,13 +336,13 @@ class _FastStyleFn(torch.autograd.Function):
             y = conv(a, "deconv3.conv2d", 3, 9, 1)
         out = ops.scaled_tanh(y, 3)
         sv["deconv3"] = (a, y)
-        ctx.sv, ctx.net, ctx.P, ctx.strength = sv, net, P, strength
+        ctx.sv, ctx.net, ctx.P, ctx.strength, ctx.norm = sv, net, P, strength, norm
         ctx.train_w = anchor.requires_grad
         return feats, out
 
     @staticmethod
     def backward(ctx, gfeat, gout):
-        sv, net, P, strength = ctx.sv, ctx.net, ctx.P, ctx.strength
+        sv, net, P, strength, norm = ctx.sv, ctx.net, ctx.P, ctx.strength, ctx.norm
         train_w = ctx.train_w
 
         def wgrad(mod, inp, dy, k, st, db=False):
@@ -290,7 +394,7 @@ class _FastStyleFn(torch.autograd.Function):
             for name in ("deconv2", "deconv1"):
                 up, y, s = sv[name]
                 layer = getattr(net, name)
-                dy = in_bwd(g, y, s, layer.instance, layer.conv2d, "relu")
+                dy = norm.bwd(g, y, s, layer.instance, layer.conv2d, train_w)
                 wgrad(layer.conv2d, up, dy, 3, 1)
                 g = ops.upsample2x_bwd(dgrad(dy, name + ".conv2d", up, 3, 1))
         if gfeat is not None:
@@ -300,7 +404,7 @@ class _FastStyleFn(torch.autograd.Function):
             else:
                 ops.axpby(gfeat, g, 1.0, 1.0)
         if g is None:
-            return None, None, None, None
+            return None, None, None, None, None
         gh = g
         for i in reversed(range(5)):
             blk = net.blocks()[i]
@@ -317,14 +421,14 @@ class _FastStyleFn(torch.autograd.Function):
         for name, k, st in (("conv3", 3, 2), ("conv2", 3, 2), ("conv1", 9, 1)):
             a_in, y, s = sv[name]
             layer = getattr(net, name)
-            dy = in_bwd(g, y, s, layer.instance, layer.conv2d, "relu")
+            dy = norm.bwd(g, y, s, layer.instance, layer.conv2d, train_w)
             wgrad(layer.conv2d, a_in, dy, k, st)
             if name != "conv1":
                 g = dgrad(dy, name + ".conv2d", a_in, k, st)
             elif ctx.needs_input_grad[0]:
                 gx = dgrad(dy, name + ".conv2d", a_in, k, st)
         ctx.sv = None
-        return gx, None, None, None
+        return gx, None, None, None, None
 
 
 class Johnson:
@@ -398,6 +502,87 @@ class Johnson:
     def infer_method(self, frame):
         """fs_johnson.py:50-52: styled frame / 255."""
         _, styled = self.model(frame.to(self.device).float())
+        return styled / 255.0
+
+
+class Dumoulin(Johnson):
+    """fs_dumoulin.py:6-58: one net for ``n_styles = len(style_imgs)`` styles.  Each step styles the batch with ONE
+    style id (fast_style_transfer.py:230-246: a np.random.randint(0, n_styles) draw per iteration, 0 for a single
+    style) and takes content = alpha * mse(relu3_3) and style = beta * sum_levels mean((Gram - styles[id][level])^2);
+    no TV term, no temporal term.  Adam covers every parameter with dense gradients, so the embedding rows of the
+    styles not drawn get a zero gradient (their Adam moments still decay).
+    emphasis: one (alpha, beta) pair, or a list of one pair per style."""
+
+    def __init__(self, style_imgs, emphasis=(1.0, 1e5), lr=1e-3, batch_sz=16, device="cuda", vgg=None, model=None):
+        self.n_styles = len(style_imgs)
+        if self.n_styles < 1:
+            raise ValueError("Dumoulin: at least one style image")
+        per_style = isinstance(emphasis[0], (tuple, list))
+        self.emphasis = [tuple(e) for e in emphasis] if per_style else [tuple(emphasis)] * self.n_styles
+        if len(self.emphasis) != self.n_styles or any(len(e) != 2 for e in self.emphasis):
+            raise ValueError("Dumoulin: emphasis is one (alpha, beta) pair or one pair per style")
+        if model is None:
+            model = make_net(3, self.n_styles).to(torch.device(device))
+        super().__init__(style_imgs, self.emphasis[0] + (0.0,), lr, batch_sz, device, vgg, model)
+
+    def draw_style(self):
+        """fast_style_transfer.py:237-240: one np.random.randint(0, n_styles) draw; no draw for a single style."""
+        if self.n_styles == 1:
+            return 0
+        import numpy as np
+        return int(np.random.randint(0, self.n_styles))
+
+    def _check_style(self, style_id):
+        style_id = int(style_id)
+        if not 0 <= style_id < self.n_styles:
+            raise ValueError("Dumoulin: style id %d outside [0, %d)" % (style_id, self.n_styles))
+        return style_id
+
+    def _style_targets(self, B, style_id=0):
+        if (B, style_id) not in self._gram_cache:
+            self._gram_cache[(B, style_id)] = [g.expand(B, -1, -1).contiguous() for g in self.styles[style_id]]
+        return self._gram_cache[(B, style_id)]
+
+    def _forward_nhwc(self, x, style_id):
+        if isinstance(self.model, MultiStyleNet):
+            return self.model.forward_nhwc(x, s_id=style_id)
+        return self.model.forward_nhwc(x)
+
+    def losses_nhwc(self, img_nhwc, style_id):
+        """train_method's loss graph (fs_dumoulin.py:26-49) on an NHWC4 [0,1] image batch with the host style id
+        -> (loss, content, style, styled), the reference's tuple order + the styled image (NHWC4, 0..255)."""
+        style_id = self._check_style(style_id)
+        alpha, beta = self.emphasis[style_id]
+        _, styled = self._forward_nhwc(img_nhwc, style_id)
+        with torch.no_grad():
+            xc = perceptual.normalize_nhwc(img_nhwc)
+        styled_f, img_f = self.vgg.forward_multi_nhwc([perceptual.normalize_nhwc(styled, d0=255.0), xc],
+                                                      [len(self.vgg.slices_idx), 3])
+        content = perceptual.mse_loss(styled_f[2], img_f[2], alpha)
+        style = None
+        for f, gs in zip(styled_f, self._style_targets(img_nhwc.shape[0], style_id)):
+            t = perceptual.mse_loss(perceptual.gram_nhwc(f), gs, beta)
+            style = t if style is None else style + t
+        return content + style, content, style, styled
+
+    def train_step(self, img, style_id=None):
+        """prep_adam + train_method + adam.step for one [B,3,H,W] batch in [0,1].  style_id None: drawn as the
+        reference's loop does (draw_style).  Returns ((total, content, style) as device scalars, styled NHWC4
+        0..255)."""
+        if style_id is None:
+            style_id = self.draw_style()
+        self.prep_adam(self.itr)
+        x = ops.nchw_to_nhwc(img.to(self.device).float().contiguous())
+        loss, cl, sl, styled = self.losses_nhwc(x, style_id)
+        loss.backward()
+        self.adam.step()
+        self.itr += 1
+        return (loss.detach(), cl.detach(), sl.detach()), styled
+
+    @torch.no_grad()
+    def infer_method(self, frame, style_id=0):
+        """fs_dumoulin.py:56-58: styled frame / 255."""
+        _, styled = self.model(frame.to(self.device).float(), s_id=style_id)
         return styled / 255.0
 
 

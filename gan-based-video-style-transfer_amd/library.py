@@ -12,6 +12,8 @@ library's NHWC layout on the device.  Backward passes are themselves ``vst::`` o
   vst::conv_transpose2d(x, weight, bias?, stride, padding, output_padding)   nn.ConvTranspose2d
         networks.py:408-416 (up-sampling layers)
   vst::instance_norm_act(x, act, slope)        InstanceNorm2d(affine=False) + ReLU / LeakyReLU / none
+  vst::cond_instance_norm(x, sid, embed, bn_weight, bn_bias, act)   learning-based network.py:120-145
+        ConditionalBatchNorm2d (+ ReLU); sid a device int32 [N], the embedding rows gathered by the kernel
   vst::warp_bilinear(x, flow)                  utils/flowtools.py:18-32 (F.grid_sample, zeros)
   vst::fbcheck(flow_fw, flow_bw)               utils/flowtools.py:34-58 (fbcCheckTorch)
   vst::temporal_loss(a, b, flow, mask, lam)    CycleGANCon cycle_gan_model.py:191-204
@@ -243,6 +245,67 @@ def _in_bwd(ctx, grad):
 
 
 instance_norm_act.register_autograd(_in_bwd, setup_context=_in_setup)
+
+
+# ------------------------------------------------------------------------ cond_instance_norm
+def _cond_args(x, sid, embed, bn_weight, bn_bias, act):
+    if act not in ("none", "relu"):
+        raise ValueError("vst::cond_instance_norm: act must be 'none' or 'relu'")
+    ops._dev_check(x, embed, bn_weight, bn_bias)
+    C = x.shape[1]
+    if bn_weight.numel() != C or bn_bias.numel() != C or tuple(embed.shape[1:]) != (2 * C,):
+        raise ValueError("vst::cond_instance_norm: bn_weight / bn_bias [C] and embed [S, 2*C] for x [N, C, H, W]")
+    y = _nhwc(x)
+    return y, ops.instnorm_stats(y), embed.detach().contiguous(), bn_weight.detach().contiguous(), \
+        bn_bias.detach().contiguous()
+
+
+@torch.library.custom_op("vst::cond_instance_norm", mutates_args=())
+def cond_instance_norm(x: Tensor, sid: Tensor, embed: Tensor, bn_weight: Tensor, bn_bias: Tensor,
+                       act: str) -> Tensor:
+    """network.py:120-145 ConditionalBatchNorm2d (+ ReLU): act(ge * InstanceNorm2d(affine=True)(x) + be) with
+    {ge, be} = embed[sid[n]].chunk(2); sid a device int32 [N] (one style per sample; the reference's 0-dim id is
+    that id N times), embed [S, 2*C].  act in none | relu."""
+    y, st, e, w, b = _cond_args(x, sid, embed, bn_weight, bn_bias, act)
+    return ops.nhwc_to_nchw(ops.cond_instnorm_fwd(y, st, sid, e, w, b, act), x.shape[1])
+
+
+@cond_instance_norm.register_fake
+def _(x, sid, embed, bn_weight, bn_bias, act):
+    return torch.empty_like(x)
+
+
+@torch.library.custom_op("vst::cond_instance_norm_backward", mutates_args=())
+def cond_instance_norm_backward(grad: Tensor, x: Tensor, sid: Tensor, embed: Tensor, bn_weight: Tensor,
+                                bn_bias: Tensor, act: str) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(dx, dembed, dbn_weight, dbn_bias) of vst::cond_instance_norm; dembed is dense: rows of styles absent
+    from sid are zero."""
+    y, st, e, w, b = _cond_args(x, sid, embed, bn_weight, bn_bias, act)
+    de, dw, db = torch.empty_like(e), torch.empty_like(w), torch.empty_like(b)
+    dx = ops.cond_instnorm_bwd(_nhwc(grad), y, st, sid, e, w, b, act, dembed=de, dbn_w=dw, dbn_b=db,
+                               accumulate=False)
+    return ops.nhwc_to_nchw(dx, x.shape[1]), de, dw, db
+
+
+@cond_instance_norm_backward.register_fake
+def _(grad, x, sid, embed, bn_weight, bn_bias, act):
+    return torch.empty_like(x), torch.empty_like(embed), torch.empty_like(bn_weight), torch.empty_like(bn_bias)
+
+
+def _cin_setup(ctx, inputs, output):
+    x, sid, embed, bn_weight, bn_bias, act = inputs
+    ctx.save_for_backward(x, sid, embed, bn_weight, bn_bias)
+    ctx.act = act
+
+
+def _cin_bwd(ctx, grad):
+    x, sid, embed, bn_weight, bn_bias = ctx.saved_tensors
+    dx, de, dw, db = torch.ops.vst.cond_instance_norm_backward(grad.contiguous(), x, sid, embed, bn_weight, bn_bias,
+                                                               ctx.act)
+    return dx, None, de, dw, db, None
+
+
+cond_instance_norm.register_autograd(_cin_bwd, setup_context=_cin_setup)
 
 
 # ------------------------------------------------------------------------------------ flow
@@ -537,4 +600,4 @@ OPS: List[str] = ["conv2d", "conv2d_backward", "conv_transpose2d", "conv_transpo
                   "instance_norm_act", "instance_norm_act_backward", "warp_bilinear", "warp_bilinear_backward",
                   "fbcheck", "temporal_loss", "temporal_loss_backward", "temporal_sqdiff", "temporal_sqdiff_backward",
                   "resize_bilinear", "gram", "gram_backward", "adam_", "ruder_stack", "ruder_stack_backward",
-                  "ruder_temporal", "ruder_temporal_backward"]
+                  "ruder_temporal", "ruder_temporal_backward", "cond_instance_norm", "cond_instance_norm_backward"]

@@ -984,6 +984,73 @@ def instnorm_affine_bwd(g, y, stats, gamma, beta, act="none", gate=None, gate_mu
     return dx
 
 
+def style_ids(s_id, N, S, device):
+    """The device int32 [N] style ids the conditional-norm kernels read, from a Python int, a 0-dim tensor
+    (long or float: truncated as ``.long()`` does; one style for the batch) or a length-N sequence / 1-D tensor
+    (one style per sample).  Values that arrive on the host are range-checked here (ValueError); a device
+    tensor is converted on the device without a copy back, and the kernels clamp what they read."""
+    if torch.is_tensor(s_id):
+        if s_id.dim() > 1 or (s_id.dim() == 1 and s_id.numel() != N):
+            raise ValueError("style id: a scalar or %d ids, got shape %s" % (N, tuple(s_id.shape)))
+        if s_id.is_cuda:
+            return s_id.detach().to(torch.int64).to(torch.int32).expand(N).contiguous()
+        s_id = s_id.detach().to(torch.int64).tolist()
+    try:
+        ids = [int(v) for v in s_id]
+    except TypeError:
+        ids = [int(s_id)] * N
+    if len(ids) != N:
+        raise ValueError("style id: a scalar or %d ids, got %d" % (N, len(ids)))
+    if min(ids) < 0 or max(ids) >= S:
+        raise ValueError("style id %s outside [0, %d)" % (ids if len(set(ids)) > 1 else ids[0], S))
+    return torch.tensor(ids, dtype=torch.int32, device=device)
+
+
+def _cond_check(y, stats, sid, embed, bn_w, bn_b, act):
+    _dev_check(y, stats, embed, bn_w, bn_b)
+    N, C = y.shape[0], y.shape[-1]
+    if not sid.is_cuda or sid.dtype != torch.int32 or not sid.is_contiguous() or tuple(sid.shape) != (N,):
+        raise RuntimeError("cond_instnorm: sid must be a contiguous int32 GPU tensor of %d ids" % N)
+    S, Cl = embed.shape[0], bn_w.numel()
+    if y.dim() != 4 or tuple(stats.shape) != (N, C, 2) or tuple(embed.shape) != (S, 2 * Cl) or \
+            bn_b.numel() != Cl or not 0 < Cl <= C or S < 1:
+        raise ValueError("cond_instnorm: y NHWC with stats [N, C, 2], embed [S, 2*Cl] and bn weight / bias [Cl], "
+                         "Cl <= %d" % C)
+    if act not in ("none", "relu"):
+        raise ValueError("cond_instnorm: act must be 'none' or 'relu'")
+    return S, Cl
+
+
+def cond_instnorm_fwd(y, stats, sid, embed, bn_w, bn_b, act="none"):
+    """act(ge * (bn_w * IN(y) + bn_b) + be), {ge, be} = the halves of embed[sid[n]] (vst_cond_instnorm_fwd).
+    sid: device int32 [N] (style_ids); embed [S, 2*Cl], bn_w / bn_b [Cl], Cl <= C real channels."""
+    S, Cl = _cond_check(y, stats, sid, embed, bn_w, bn_b, act)
+    N, H, W, C = y.shape
+    out = torch.empty_like(y)
+    ws = torch.empty((N, C, 2), device=y.device)
+    _call("vst_cond_instnorm_fwd", _p(y), _p(stats), _p(sid), _p(embed), _p(bn_w), _p(bn_b), _p(out), _p(ws),
+          N, H * W, C, Cl, S, ACT[act], _stream())
+    return out
+
+
+def cond_instnorm_bwd(g, y, stats, sid, embed, bn_w, bn_b, act="none", dembed=None, dbn_w=None, dbn_b=None,
+                      dbias=None, accumulate=True):
+    """dx of cond_instnorm_fwd; dembed [S, 2*Cl] (every row), dbn_w, dbn_b, dbias [Cl] written or accumulated."""
+    S, Cl = _cond_check(y, stats, sid, embed, bn_w, bn_b, act)
+    _dev_check(g, dembed, dbn_w, dbn_b, dbias)
+    N, H, W, C = y.shape
+    if g.shape != y.shape or (dembed is not None and dembed.numel() != S * 2 * Cl) or \
+            any(t is not None and t.numel() != Cl for t in (dbn_w, dbn_b, dbias)):
+        raise ValueError("cond_instnorm_bwd: g as y, dembed [S, 2*Cl], dbn_w / dbn_b / dbias [Cl]")
+    dx = torch.empty_like(y)
+    nbytes = lib().vst_cond_instnorm_ws_bytes(N, H * W, C)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=y.device)
+    _call("vst_cond_instnorm_bwd", _p(g), _p(y), _p(stats), _p(sid), _p(embed), _p(bn_w), _p(bn_b), _p(dx),
+          _p(dembed), _p(dbn_w), _p(dbn_b), _p(dbias), _p(ws), N, H * W, C, Cl, S, ACT[act],
+          1 if accumulate else 0, _stream())
+    return dx
+
+
 def upsample2x(x):
     _dev_check(x)
     N, H, W, C = x.shape

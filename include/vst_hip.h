@@ -33,6 +33,7 @@
  *   vst_ruder_*                 methods/learning-based/fs_ruder.py:38-108 recurrence: input stacking, temporal loss
  *   vst_instnorm_affine_*       nn.InstanceNorm2d(affine=True) (+ReLU, + ResidualBlock layer_strength
  *                               gate) of methods/learning-based/network.py:147-298 (FastStyleNet)
+ *   vst_cond_instnorm_*         ConditionalBatchNorm2d (+ReLU) of network.py:120-217 (FastStyleNet, n_styles > 1)
  *   vst_upsample2x_*            F.interpolate(scale_factor=2) in network.py:206-207
  *   vst_scaled_tanh_*           ConvTanh network.py:111-118
  *   vst_channel_normalize       fast_style_transfer.py:819-822 normalize (+ the fs_johnson.py:31 /255)
@@ -490,6 +491,26 @@ int vst_instnorm_affine_bwd(const float* gy, const float* x, const float* stats,
                             const float* beta, const float* gate, float gate_mult, float* dx,
                             float* dgamma, float* dbeta, float* dgate, float* dbias, float* ws, int N,
                             int HW, int C, int act, float slope, int accumulate, void* stream);
+/* Conditional instance norm (ConditionalBatchNorm2d, network.py:120-145): per sample n with s = sid[n],
+ * y = act(ge * (w[c] * xhat + b[c]) + be), ge = embed[s][c], be = embed[s][Cl + c]; embed [S][2*Cl], bn_weight
+ * and bn_bias [Cl] (the inner InstanceNorm2d(affine=True)), stats from vst_instnorm_stats.  x, y NHWC with C
+ * channels (a multiple of 4, at most 1024), of which the first Cl <= C are real: channels c >= Cl of y and dx are
+ * written 0.  sid: DEVICE int32 [N], read by the kernels and clamped there to [0, S-1] (no host copy of it is
+ * made); act VST_ACT_NONE or VST_ACT_RELU.  The affine map is folded per (n, c) into z = x * al + sh,
+ * al = rstd * ge * w, sh = (ge * b + be) - mean * al.  fwd: ws of at least N*C*2 floats (the head of a
+ * vst_cond_instnorm_ws_bytes buffer serves).
+ * Backward: dx written; dembed [S][2*Cl] (EVERY row, zeros for a style no sample carries), dbn_weight, dbn_bias
+ * [Cl] and dbias [Cl] (the gradient of a conv bias feeding the norm: the per-channel sum of dx) each may be NULL,
+ * and are written or accumulated (accumulate != 0).  All reductions fp64 in a fixed order over the slices and
+ * over n, no atomics.  ws: vst_cond_instnorm_ws_bytes bytes (0 for a C the kernels do not take). */
+size_t vst_cond_instnorm_ws_bytes(int N, int HW, int C);
+int vst_cond_instnorm_fwd(const float* x, const float* stats, const int* sid, const float* embed,
+                          const float* bn_weight, const float* bn_bias, float* y, float* ws, int N, int HW,
+                          int C, int Cl, int S, int act, void* stream);
+int vst_cond_instnorm_bwd(const float* gy, const float* x, const float* stats, const int* sid,
+                          const float* embed, const float* bn_weight, const float* bn_bias, float* dx,
+                          float* dembed, float* dbn_weight, float* dbn_bias, float* dbias, float* ws, int N,
+                          int HW, int C, int Cl, int S, int act, int accumulate, void* stream);
 /* Nearest 2x upsample of NHWC (Cs % 4 == 0): y [N][2H][2W][Cs]; backward sums each 2x2 block. */
 int vst_upsample2x_fwd(const float* x, float* y, int N, int H, int W, int Cs, void* stream);
 int vst_upsample2x_bwd(const float* gy, float* gx, int N, int H, int W, int Cs, void* stream);
