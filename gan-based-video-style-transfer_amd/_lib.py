@@ -131,6 +131,9 @@ SIGNATURES = {
     "vst_cond_instnorm_ws_bytes": (SZ, [I, I, I]),
     "vst_cond_instnorm_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "vst_cond_instnorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "vst_instnorm_skip_ws_bytes": (SZ, [I, I, I]),
+    "vst_instnorm_skip_fwd": (I, [P, P, P, P, I, I, I, I, I, F, P]),
+    "vst_instnorm_skip_bwd": (I, [P, P, I, I, P, P, P, P, I, P, I, I, I, F, P]),
     "vst_upsample2x_fwd": (I, [P, P, I, I, I, I, P]),
     "vst_upsample2x_bwd": (I, [P, P, I, I, I, I, P]),
     "vst_scaled_tanh_fwd": (I, [P, P, L, I, I, P]),

@@ -943,9 +943,239 @@ __global__ void in_stats_from_running_k(const float* __restrict__ rm, const floa
   stats[2 * i + 1] = 1.f / sqrtf(rv[c] + eps);
 }
 
+// ---- U-Net skip connection (UnetSkipConnectionBlock, GAN-based networks.py:468-535) --------------
+// z = IN(y) (or y itself below the outermost block) feeds two readers: the child's in-place
+// LeakyReLU (d = lrelu(z), the child down conv's input) and, through the parent's in-place ReLU over
+// the concatenation, the skip half relu(lrelu(z)) = relu(z).  One pass reads y and writes both, the
+// skip half straight into channels [c0, c0 + C) of the concatenation buffer (row stride Cs): 12 B per
+// element instead of two applies and a channel copy (24 B).  The backward forms
+// g = g_d * lrelu'(z) + g_s * relu'(z) from the child conv's data gradient g_d and the skip half of
+// the parent up conv's data gradient read in place (g_cat at c0, stride Cs), then the IN backward.
+__device__ __forceinline__ void skip_z4(float4& v, const float* __restrict__ stats, long nc4) {
+  const float4* st = reinterpret_cast<const float4*>(stats) + nc4 * 2;
+  const float4 s0 = st[0], s1 = st[1];  // {m0,r0,m1,r1}, {m2,r2,m3,r3}
+  v.x = (v.x - s0.x) * s0.y;
+  v.y = (v.y - s0.z) * s0.w;
+  v.z = (v.z - s1.x) * s1.y;
+  v.w = (v.w - s1.z) * s1.w;
+}
+
+// the combined pre-activation gradient; lrelu'(0) = slope, relu'(0) = 0
+__device__ __forceinline__ float skip_g(float gd, float gs, float z, float slope) {
+  return z > 0.f ? gd + gs : gd * slope;
+}
+
+// STATS / HAS_D: the variants carry their own names in a kernel trace (12 B per element with both outputs, 8 B
+// as the up norm's apply)
+template <bool STATS, bool HAS_D>
+__global__ void skip_apply_k(const float4* __restrict__ y, const float* __restrict__ stats,
+                             float4* __restrict__ d, float* __restrict__ cat, long total4, int HW, int C4,
+                             int Cs, int c0, float slope) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total4) return;
+  const int c4 = i % C4;
+  const long pix = i / C4;
+  float4 v = y[i];
+  if (STATS) skip_z4(v, stats, (pix / HW) * C4 + c4);
+  if (HAS_D)
+    d[i] = make_float4(v.x > 0.f ? v.x : v.x * slope, v.y > 0.f ? v.y : v.y * slope,
+                       v.z > 0.f ? v.z : v.z * slope, v.w > 0.f ? v.w : v.w * slope);
+  *reinterpret_cast<float4*>(cat + pix * Cs + c0 + 4 * c4) =
+      make_float4(v.x > 0.f ? v.x : 0.f, v.y > 0.f ? v.y : 0.f, v.z > 0.f ? v.z : 0.f, v.w > 0.f ? v.w : 0.f);
+}
+
+// in_partial_k<1>'s slices over the combined gradient: STATS {sum g, sum g*xhat, sum xhat} per
+// (n, slice, c); without stats {sum g} alone (z = y, the bias gradient's partials).
+template <bool STATS>
+__global__ __launch_bounds__(NRED) void skip_partial_k(const float* __restrict__ gd, const float* __restrict__ gcat,
+                                                       const float* __restrict__ y, const float* __restrict__ stats,
+                                                       double* __restrict__ part, int HW, int C, int Cs, int c0,
+                                                       int LP, int PG, int SP, int nsplit, float slope) {
+  constexpr int NV = STATS ? 3 : 1;
+  __shared__ double red[NV * 4][NRED];
+  const int t = threadIdx.x, c4 = t % LP, pg = t / LP;
+  const int n = blockIdx.y, z = blockIdx.x;
+  const int p0 = z * SP, p1 = min(HW, p0 + SP);
+  double acc[NV][4];
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[v][j] = 0.0;
+  const float4* yb = reinterpret_cast<const float4*>(y) + (long)n * HW * LP + c4;
+  const float4* db = gd ? reinterpret_cast<const float4*>(gd) + (long)n * HW * LP + c4 : nullptr;
+  const float* sb = gcat + (long)n * HW * Cs + c0 + 4 * c4;
+  const long nc4 = (long)n * LP + c4;
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto accum = [&](float4 v, const float4 a, const float4 b) {
+    if (STATS) skip_z4(v, stats, nc4);
+    const float zz[4] = {v.x, v.y, v.z, v.w};
+    const float ga[4] = {a.x, a.y, a.z, a.w}, gb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float g = skip_g(ga[j], gb[j], zz[j], slope);
+      acc[0][j] += g;
+      if (STATS) {
+        acc[1][j] += (double)g * zz[j];
+        acc[2][j] += zz[j];
+      }
+    }
+  };
+  // rows p, p + PG, ... in that order; UR rows' loads issued ahead of their serial fp64 accumulation
+  constexpr int UR = IN_UNROLL;
+  if (pg < PG) {
+    int p = p0 + pg;
+    for (; p + (UR - 1) * PG < p1; p += UR * PG) {
+      float4 v[UR], a[UR], b[UR];
+#pragma unroll
+      for (int k = 0; k < UR; ++k) {
+        const long q = p + k * PG;
+        v[k] = yb[q * LP];
+        a[k] = db ? db[q * LP] : z4;
+        b[k] = *reinterpret_cast<const float4*>(sb + q * Cs);
+      }
+#pragma unroll
+      for (int k = 0; k < UR; ++k) accum(v[k], a[k], b[k]);
+    }
+    for (; p < p1; p += PG)
+      accum(yb[(long)p * LP], db ? db[(long)p * LP] : z4, *reinterpret_cast<const float4*>(sb + (long)p * Cs));
+  }
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[v * 4 + j][t] = acc[v][j];
+  __syncthreads();
+  if (pg == 0) {
+    double* dst = part + (((long)n * nsplit + z) * C + 4 * c4) * NV;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        double s = 0.0;
+        for (int q = 0; q < PG; ++q) s += red[v * 4 + j][q * LP + c4];
+        dst[j * NV + v] = s;
+      }
+  }
+}
+
+// without stats the slices hold the gradient's sums alone: dbn[n][c] = sum_z part[n][z][c]
+template <int CPB>
+__global__ void skip_db_finalize_k(const double* __restrict__ part, double* __restrict__ dbn, int C, int nsplit) {
+  double a[1];
+  const int n = blockIdx.y;
+  if (!fold_slices<1, CPB>(part, n, C, nsplit, a)) return;
+  dbn[n * C + blockIdx.x * CPB + (threadIdx.x % CPB)] = a[0];
+}
+
+// grid max(ceil(total4 / 256), ceil(C / 256)) so that the first blocks cover every channel's bias gradient
+template <bool STATS, bool HAS_GD>
+__global__ void skip_bwd_apply_k(const float4* __restrict__ gd, const float* __restrict__ gcat,
+                                 const float4* __restrict__ y, const float* __restrict__ stats,
+                                 const float2* __restrict__ coef, float4* __restrict__ dy, long total4, int HW,
+                                 int C4, int Cs, int c0, float slope, const double* __restrict__ dbn,
+                                 float* __restrict__ db, int N, int accumulate_db) {
+  if (db && blockIdx.x * blockDim.x < 4 * C4)
+    in_bias_grad_blocks(dbn, db, N, 4 * C4, accumulate_db, blockIdx.x * blockDim.x + threadIdx.x);
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total4) return;
+  const int c4 = i % C4;
+  const long pix = i / C4;
+  const long nc4 = (pix / HW) * C4 + c4;
+  float4 v = y[i];
+  if (STATS) skip_z4(v, stats, nc4);
+  const float4 a = HAS_GD ? gd[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 b = *reinterpret_cast<const float4*>(gcat + pix * Cs + c0 + 4 * c4);
+  float4 o = make_float4(skip_g(a.x, b.x, v.x, slope), skip_g(a.y, b.y, v.y, slope), skip_g(a.z, b.z, v.z, slope),
+                         skip_g(a.w, b.w, v.w, slope));
+  if (STATS) {
+    const float4* st = reinterpret_cast<const float4*>(stats) + nc4 * 2;
+    const float4 s0 = st[0], s1 = st[1];
+    const float4 k01 = reinterpret_cast<const float4*>(coef)[nc4 * 2];
+    const float4 k23 = reinterpret_cast<const float4*>(coef)[nc4 * 2 + 1];
+    o.x = s0.y * (o.x - k01.x - v.x * k01.y);
+    o.y = s0.w * (o.y - k01.z - v.y * k01.w);
+    o.z = s1.y * (o.z - k23.x - v.z * k23.y);
+    o.w = s1.w * (o.w - k23.z - v.w * k23.w);
+  }
+  dy[i] = o;
+}
+
 }  // namespace vst
 
 using namespace vst;
+
+// ---- U-Net skip connection ------------------------------------------------------------------------
+// workspace of vst_instnorm_skip_bwd: vst_instnorm_ws_bytes' layout (slice partials [N][nsplit][C][3]
+// fp64, the {mean g, mean g*xhat} table, the per-image bias sums [N][C] fp64)
+extern "C" size_t vst_instnorm_skip_ws_bytes(int N, int HW, int C) {
+  RedGeom g;
+  if (N <= 0 || HW <= 0 || !red_geom(N, HW, C, g)) return 0;
+  return (size_t)N * g.nsplit * C * 3 * sizeof(double) + (size_t)N * C * (sizeof(float2) + sizeof(double)) + 256;
+}
+
+// VST_EINVAL for null / non-positive arguments, VST_EUNSUPPORTED for a geometry outside the contract
+static int skip_args(const char* what, bool ptrs, int N, int HW, int C, int Cs, int c0, RedGeom& g) {
+  VST_REQUIRE(ptrs && N > 0 && HW > 0 && C > 0 && Cs > 0 && c0 >= 0, "%s: null pointer or non-positive size", what);
+  if (C % 4 || c0 % 4 || Cs % 4 || (long)c0 + C > Cs || C > 4 * NRED || !red_geom(N, HW, C, g)) {
+    set_error("%s: C %% 4 == 0, c0 %% 4 == 0, Cs %% 4 == 0, c0 + C <= Cs and C <= 1024 (C %d, c0 %d, Cs %d)", what,
+              C, c0, Cs);
+    return VST_EUNSUPPORTED;
+  }
+  return VST_OK;
+}
+
+extern "C" int vst_instnorm_skip_fwd(const float* y, const float* stats, float* d, float* cat, int N, int HW, int C,
+                                     int Cs, int c0, float slope, void* stream) {
+  RedGeom g;
+  if (const int rc = skip_args("instnorm_skip_fwd", y && cat, N, HW, C, Cs, c0, g)) return rc;
+  const long total4 = (long)N * HW * C / 4;
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(ceil_div(total4, 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(y), stats, reinterpret_cast<float4*>(d), cat, total4, HW, C / 4,
+                       Cs, c0, slope);
+  };
+  if (stats) d ? launch(skip_apply_k<true, true>) : launch(skip_apply_k<true, false>);
+  else d ? launch(skip_apply_k<false, true>) : launch(skip_apply_k<false, false>);
+  return check_launch("instnorm_skip_fwd");
+}
+
+extern "C" int vst_instnorm_skip_bwd(const float* g_d, const float* g_cat, int Cs, int c0, const float* y,
+                                     const float* stats, float* dy, float* db, int accumulate_db, float* ws, int N,
+                                     int HW, int C, float slope, void* stream) {
+  RedGeom g;
+  if (const int rc = skip_args("instnorm_skip_bwd", g_cat && y && dy && (ws || (!stats && !db)), N, HW, C, Cs, c0, g))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  double* part = reinterpret_cast<double*>(ws);
+  float2* coef = reinterpret_cast<float2*>(reinterpret_cast<char*>(ws) + (size_t)N * g.nsplit * C * 3 * sizeof(double));
+  double* dbn = reinterpret_cast<double*>(reinterpret_cast<char*>(coef) + (size_t)N * C * sizeof(float2));
+  const bool narrow = fin_cpb(C, N, g.nsplit) == 4;
+  const dim3 fgrid(ceil_div(C, narrow ? 4 : 16), N);
+  if (stats) {
+    hipLaunchKernelGGL(skip_partial_k<true>, dim3(g.nsplit, N), dim3(NRED), 0, s, g_d, g_cat, y, stats, part, HW, C,
+                       Cs, c0, g.LP, g.PG, g.SP, g.nsplit, slope);
+    if (narrow)
+      hipLaunchKernelGGL(in_bwd_finalize_k<4>, fgrid, dim3(256), 0, s, part, stats, coef, dbn, N, HW, C, g.nsplit);
+    else
+      hipLaunchKernelGGL(in_bwd_finalize_k<16>, fgrid, dim3(256), 0, s, part, stats, coef, dbn, N, HW, C, g.nsplit);
+  } else if (db) {
+    hipLaunchKernelGGL(skip_partial_k<false>, dim3(g.nsplit, N), dim3(NRED), 0, s, g_d, g_cat, y, stats, part, HW, C,
+                       Cs, c0, g.LP, g.PG, g.SP, g.nsplit, slope);
+    if (narrow)
+      hipLaunchKernelGGL(skip_db_finalize_k<4>, fgrid, dim3(256), 0, s, part, dbn, C, g.nsplit);
+    else
+      hipLaunchKernelGGL(skip_db_finalize_k<16>, fgrid, dim3(256), 0, s, part, dbn, C, g.nsplit);
+  }
+  const long total4 = (long)N * HW * C / 4;
+  const int blocks = std::max(ceil_div(total4, 256), ceil_div(C, 256));
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(g_d), g_cat,
+                       reinterpret_cast<const float4*>(y), stats, coef, reinterpret_cast<float4*>(dy), total4, HW,
+                       C / 4, Cs, c0, slope, dbn, db, N, accumulate_db);
+  };
+  if (stats) g_d ? launch(skip_bwd_apply_k<true, true>) : launch(skip_bwd_apply_k<true, false>);
+  else g_d ? launch(skip_bwd_apply_k<false, true>) : launch(skip_bwd_apply_k<false, false>);
+  return check_launch("instnorm_skip_bwd");
+}
 
 extern "C" size_t vst_instnorm_ws_bytes(int N, int HW, int C) {
   RedGeom g;

@@ -14,6 +14,8 @@ library's NHWC layout on the device.  Backward passes are themselves ``vst::`` o
   vst::instance_norm_act(x, act, slope)        InstanceNorm2d(affine=False) + ReLU / LeakyReLU / none
   vst::cond_instance_norm(x, sid, embed, bn_weight, bn_bias, act)   learning-based network.py:120-145
         ConditionalBatchNorm2d (+ ReLU); sid a device int32 [N], the embedding rows gathered by the kernel
+  vst::instance_norm_skip(y, normalize, slope) GAN-based networks.py:468-535, the U-Net skip connection under its
+        in-place activations: (lrelu(z), relu(z)), z = InstanceNorm2d(affine=False)(y) or y (normalize=False)
   vst::warp_bilinear(x, flow)                  utils/flowtools.py:18-32 (F.grid_sample, zeros)
   vst::fbcheck(flow_fw, flow_bw)               utils/flowtools.py:34-58 (fbcCheckTorch)
   vst::temporal_loss(a, b, flow, mask, lam)    CycleGANCon cycle_gan_model.py:191-204
@@ -308,6 +310,56 @@ def _cin_bwd(ctx, grad):
 cond_instance_norm.register_autograd(_cin_bwd, setup_context=_cin_setup)
 
 
+# ------------------------------------------------------------------------ instance_norm_skip
+@torch.library.custom_op("vst::instance_norm_skip", mutates_args=())
+def instance_norm_skip(y: Tensor, normalize: bool, slope: float) -> Tuple[Tensor, Tensor]:
+    """networks.py:468-535 UnetSkipConnectionBlock's skip connection as its readers see it: with z =
+    InstanceNorm2d(affine=False, eps=1e-5)(y) (normalize=False: z = y), returns (d, skip) = (LeakyReLU(slope)(z) —
+    the child's in-place activation, the next down conv's input —, ReLU(z) — the skip half of the concatenation
+    after the parent's in-place ReLU).  One pass over y (vst_instnorm_skip_fwd)."""
+    ops._dev_check(y)
+    C = y.shape[1]
+    yn = _nhwc(y)
+    skip = torch.empty_like(yn)
+    d = ops.instnorm_skip_fwd(yn, ops.instnorm_stats(yn) if normalize else None, skip, 0, slope=slope)
+    return ops.nhwc_to_nchw(d, C), ops.nhwc_to_nchw(skip, C)
+
+
+@instance_norm_skip.register_fake
+def _(y, normalize, slope):
+    return torch.empty_like(y), torch.empty_like(y)
+
+
+@torch.library.custom_op("vst::instance_norm_skip_backward", mutates_args=())
+def instance_norm_skip_backward(g_d: Tensor, g_skip: Tensor, y: Tensor, normalize: bool, slope: float) -> Tensor:
+    """dy of vst::instance_norm_skip from both output gradients: g = g_d * lrelu'(z) + g_skip * relu'(z), then the
+    InstanceNorm backward (vst_instnorm_skip_bwd)."""
+    ops._dev_check(g_d, g_skip, y)
+    yn = _nhwc(y)
+    dy = ops.instnorm_skip_bwd(_nhwc(g_d), _nhwc(g_skip), 0, yn, ops.instnorm_stats(yn) if normalize else None,
+                               slope=slope)
+    return ops.nhwc_to_nchw(dy, y.shape[1])
+
+
+@instance_norm_skip_backward.register_fake
+def _(g_d, g_skip, y, normalize, slope):
+    return torch.empty_like(y)
+
+
+def _ins_setup(ctx, inputs, output):
+    y, normalize, slope = inputs
+    ctx.save_for_backward(y)
+    ctx.conf = (normalize, slope)
+
+
+def _ins_bwd(ctx, g_d, g_skip):
+    (y,) = ctx.saved_tensors
+    return torch.ops.vst.instance_norm_skip_backward(g_d.contiguous(), g_skip.contiguous(), y, *ctx.conf), None, None
+
+
+instance_norm_skip.register_autograd(_ins_bwd, setup_context=_ins_setup)
+
+
 # ------------------------------------------------------------------------------------ flow
 @torch.library.custom_op("vst::warp_bilinear", mutates_args=())
 def warp_bilinear(x: Tensor, flow: Tensor) -> Tensor:
@@ -600,4 +652,5 @@ OPS: List[str] = ["conv2d", "conv2d_backward", "conv_transpose2d", "conv_transpo
                   "instance_norm_act", "instance_norm_act_backward", "warp_bilinear", "warp_bilinear_backward",
                   "fbcheck", "temporal_loss", "temporal_loss_backward", "temporal_sqdiff", "temporal_sqdiff_backward",
                   "resize_bilinear", "gram", "gram_backward", "adam_", "ruder_stack", "ruder_stack_backward",
-                  "ruder_temporal", "ruder_temporal_backward", "cond_instance_norm", "cond_instance_norm_backward"]
+                  "ruder_temporal", "ruder_temporal_backward", "cond_instance_norm", "cond_instance_norm_backward",
+                  "instance_norm_skip", "instance_norm_skip_backward"]

@@ -3,7 +3,8 @@
 Public API mirrors the reference (same names, argument meaning and errors):
   get_norm_layer (18-35), get_scheduler (38-64), init_weights (67-98), init_net (101-116),
   define_G (119-159), define_D (162-203), GANLoss (209-275), ResnetGenerator (315-373),
-  ResnetBlock (376-433), NLayerDiscriminator (538-583).
+  ResnetBlock (376-433), UnetGenerator (436-465), UnetSkipConnectionBlock (468-535),
+  NLayerDiscriminator (538-583).
 
 MI355X design (not a translation):
   * Each network keeps the reference's nn.Sequential index structure so ``state_dict()`` keys and
@@ -956,6 +957,216 @@ class _DiscriminatorFn(torch.autograd.Function):
 
 
 ###############################################################################
+# UnetGenerator (networks.py:436-535)
+###############################################################################
+class UnetSkipConnectionBlock(nn.Module):
+    """networks.py:468-535 (instance norm, no dropout): cat([x, model(x)], 1), with the reference's Sequential
+    layout so the state_dict keys match:
+        outermost  [downconv, sub, ReLU, upconv, Tanh]
+        middle     [LeakyReLU, downconv, IN, sub, ReLU, upconv, IN]
+        innermost  [LeakyReLU, downconv, ReLU, upconv, IN]"""
+
+    def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False,
+                 norm_layer=nn.BatchNorm2d, use_dropout=False):
+        super().__init__()
+        if not (isinstance(norm_layer, functools.partial) and norm_layer.func == nn.InstanceNorm2d):
+            raise NotImplementedError('only norm=instance is implemented on the HIP path')
+        if use_dropout:
+            raise NotImplementedError('dropout is not on the HIP path (CycleGAN default no_dropout)')
+        self.outermost, self.innermost = outermost, innermost
+        if input_nc is None:
+            input_nc = outer_nc
+        down = Conv2d(input_nc, inner_nc, 4, stride=2, padding=1, bias=True)
+        up = ConvTranspose2d(inner_nc if innermost else inner_nc * 2, outer_nc, 4, stride=2, padding=1, bias=True)
+        if outermost:
+            L = [down, submodule, _Marker('ReLU'), up, _Marker('Tanh')]
+        elif innermost:
+            L = [_Marker('LeakyReLU(0.2)'), down, _Marker('ReLU'), up, _Marker('InstanceNorm2d')]
+        else:
+            L = [_Marker('LeakyReLU(0.2)'), down, _Marker('InstanceNorm2d'), submodule, _Marker('ReLU'), up,
+                 _Marker('InstanceNorm2d')]
+        self.model = nn.Sequential(*L)
+        self._down, self._up = (0, 3) if outermost else ((1, 3) if innermost else (1, 5))
+
+    def convs(self):
+        return self.model[self._down], self.model[self._up]
+
+    def sub(self):
+        return None if self.innermost else self.model[1 if self.outermost else 3]
+
+
+class UnetGenerator(FlatNet):
+    """networks.py:436-465: num_downs UnetSkipConnectionBlocks, channels ngf * min(2^l, 8) at level l.  Level l's
+    block halves the resolution with Conv2d(k4, s2, p1) and doubles it back with ConvTranspose2d(k4, s2, p1);
+    what it returns is cat([its input, its up half]).  Both in-place activations of the reference run over that
+    concatenation (the child's LeakyReLU over the skip half, the parent's ReLU over all of it), so every reader of
+    it sees relu(z) / relu(IN(u)): ops.instnorm_skip_fwd writes exactly that into one buffer per level."""
+
+    def __init__(self, input_nc, output_nc, num_downs, ngf=64, norm_layer=nn.BatchNorm2d, use_dropout=False):
+        super().__init__()
+        if not (isinstance(norm_layer, functools.partial) and norm_layer.func == nn.InstanceNorm2d):
+            raise NotImplementedError('only norm=instance is implemented on the HIP path')
+        if use_dropout:
+            raise NotImplementedError('dropout is not on the HIP path (CycleGAN default no_dropout)')
+        if ngf % 4 != 0:
+            raise NotImplementedError('ngf [%d] must be a multiple of 4 on the HIP path (NHWC float4 lanes)' % ngf)
+        if num_downs < 5:
+            raise ValueError('UnetGenerator needs num_downs >= 5, got %d' % num_downs)
+        self.input_nc, self.output_nc, self.ngf, self.num_downs = input_nc, output_nc, ngf, num_downs
+        kw = dict(norm_layer=norm_layer)
+        blk = UnetSkipConnectionBlock(ngf * 8, ngf * 8, innermost=True, **kw)
+        for _ in range(num_downs - 5):
+            blk = UnetSkipConnectionBlock(ngf * 8, ngf * 8, submodule=blk, **kw)
+        blk = UnetSkipConnectionBlock(ngf * 4, ngf * 8, submodule=blk, **kw)
+        blk = UnetSkipConnectionBlock(ngf * 2, ngf * 4, submodule=blk, **kw)
+        blk = UnetSkipConnectionBlock(ngf, ngf * 2, submodule=blk, **kw)
+        self.model = UnetSkipConnectionBlock(output_nc, ngf, input_nc=input_nc, submodule=blk, outermost=True, **kw)
+        self._flatten()
+
+    def _levels(self):
+        """[(downconv, upconv)] from the outermost block (level 0) to the innermost."""
+        out, b = [], self.model
+        while b is not None:
+            out.append(b.convs())
+            b = b.sub()
+        return out
+
+    def _make_packs(self):
+        P = []
+        for l, (dn, up) in enumerate(self._levels()):
+            # the down conv's data gradient: four 2x2 phase convs (ops.conv4s2_dgrad), or the transposed kernel
+            # onto the image / below 8 channels; the up conv's forward IS such a data gradient (ops.convT4s2_fwd)
+            # and its data gradient a forward Conv2d(k4, s2, p1) over the weight read as [Co = in][Ci = out]
+            phases = l > 0 and dn.weight.shape[0] % 8 == 0
+            P.append({"dn": ops.weight_pack(dn.weight, ops.PACK_FWD),
+                      "dn_ph": ops.conv4s2_dgrad_phase_packs(dn.weight) if phases else None,
+                      "dn_ck": None if phases else ops.weight_pack(dn.weight, ops.PACK_DGRAD),
+                      "dn_b": _padded_bias(dn),
+                      "up_ph": ops.conv4s2_dgrad_phase_packs(up.weight),
+                      "up_kc": ops.weight_pack(up.weight, ops.PACK_FWD),
+                      "up_b": _padded_bias(up)})
+        return P
+
+    def _check_size(self, H, W):
+        m = 2 ** self.num_downs
+        if H % m or W % m:
+            raise ValueError('UnetGenerator with %d downsamplings needs H and W to be multiples of %d, got %d x %d'
+                             % (self.num_downs, m, H, W))
+
+    def forward(self, x):
+        self._check_size(x.shape[2], x.shape[3])
+        return super().forward(x)
+
+    def forward_nhwc(self, x):
+        self._check_size(x.shape[1], x.shape[2])
+        return _UnetFn.apply(x, self._anchor(), self)
+
+
+class _UnetFn(torch.autograd.Function):
+    """Whole U-Net forward/backward on libvst_hip kernels.  z_l = IN(y_l) (z_0 = y_0) is never stored: the skip
+    pass reads y_l once and writes d_l = lrelu(z_l) (the next down conv's input) and relu(z_l) into the skip half
+    of level l + 1's concatenation buffer; the up norm's apply writes the other half."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, net):
+        P = net.packs()
+        lv = net._levels()
+        D = len(lv)
+        role = "fwd" if any(ctx.needs_input_grad[:2]) else "infer"
+        N = x.shape[0]
+        ys, ss, ds, cats = [], [], [x], [None] * D
+        for l in range(D - 1):
+            dn, _ = lv[l]
+            cl = cpad(dn.weight.shape[0])
+            if l == 0:  # no norm follows: the bias counts
+                y, s = ops.conv2d_fwd(x, P[0]["dn"], P[0]["dn_b"], cl, 4, 4, 2, 1, "zero", role=role), None
+            else:       # the bias cancels in the norm (it keeps its exact channel-sum gradient)
+                y, s = ops.conv2d_fwd_in(ds[l], P[l]["dn"], None, cl, 4, 4, 2, 1, "zero", role=role)
+            cats[l + 1] = torch.empty((N, y.shape[1], y.shape[2], 2 * cl), device=x.device)
+            ds.append(ops.instnorm_skip_fwd(y, s, cats[l + 1], 0, slope=SLOPE))
+            ys.append(y)
+            ss.append(s)
+        dn, _ = lv[D - 1]
+        r = ops.conv2d_fwd(ds[D - 1], P[D - 1]["dn"], P[D - 1]["dn_b"], cpad(dn.weight.shape[0]), 4, 4, 2, 1, "zero",
+                           act="relu", role=role)
+        us, sus = [None] * D, [None] * D
+        inp = r
+        for l in range(D - 1, 0, -1):
+            _, up = lv[l]
+            co = cpad(up.weight.shape[1])
+            u = ops.convT4s2_fwd(inp, P[l]["up_ph"], None, co, role=role)
+            su = ops.instnorm_stats(u)
+            ops.instnorm_skip_fwd(u, su, cats[l], co, want_d=False)
+            us[l], sus[l] = u, su
+            inp = cats[l]
+        out = ops.convT4s2_fwd(inp, P[0]["up_ph"], P[0]["up_b"], cpad(net.output_nc), act="tanh", role=role)
+        if role == "fwd":
+            ctx.sv = (ys, ss, ds, cats, r, us, sus, out)
+        ctx.net, ctx.P = net, P
+        ctx.train_w = anchor.requires_grad
+        net._note_forward(ctx.train_w)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        ys, ss, ds, cats, r, us, sus, out = ctx.sv
+        net, P, train_w = ctx.net, ctx.P, ctx.train_w
+        lv = net._levels()
+        D = len(lv)
+        final = train_w and net._bwd_begin()
+
+        def done(mod):
+            if final:
+                net._grad_done(mod)
+
+        def up_grads(l, du, a_in):
+            """The up conv's weight gradient (Wt[ci][co] = the weight gradient of the conv a_in = conv(du, .)) and
+            its data gradient, that conv's forward."""
+            up = lv[l][1]
+            if train_w:
+                ci_t, co_t = up.weight.shape[0], up.weight.shape[1]
+                ops.conv2d_wgrad(du, a_in, up.weight.grad, None, 4, 4, 2, 1, "zero", ci_t, co_t, co_t * 16, 16,
+                                 accumulate=True)
+            done(up)
+            return ops.conv2d_fwd(du, P[l]["up_kc"], None, a_in.shape[-1], 4, 4, 2, 1, "zero", role="bwd")
+
+        def down_grads(l, dy, bias_here, need_dx):
+            dn = lv[l][0]
+            a_in = ds[l]
+            if train_w:
+                co, ci = dn.weight.shape[0], dn.weight.shape[1]
+                ops.conv2d_wgrad(a_in, dy, dn.weight.grad, dn.bias.grad if bias_here else None, 4, 4, 2, 1, "zero",
+                                 co, ci, ci * 16, 16, accumulate=True)
+            done(dn)
+            if not need_dx:
+                return None
+            if P[l]["dn_ph"] is not None:
+                return ops.conv4s2_dgrad(dy, P[l]["dn_ph"], a_in.shape[-1])
+            return ops.conv2d_tfwd(dy, P[l]["dn_ck"], None, a_in.shape[1], a_in.shape[2], a_in.shape[-1], 4, 4, 2, 1)
+
+        # outermost up conv + tanh (no norm after it: the bias gradient is a channel sum)
+        du = ops.act_bwd(gout.contiguous(), out, "tanh")
+        if train_w:
+            ops.channel_sum(du, lv[0][1].bias.grad, net.output_nc, accumulate=True)
+        g_cats = {1: up_grads(0, du, cats[1])}  # level -> the gradient of its concatenation buffer
+        for l in range(1, D):
+            up = lv[l][1]
+            du = ops.instnorm_skip_bwd(None, g_cats[l], cpad(up.weight.shape[1]), us[l], sus[l],
+                                       db=up.bias.grad if train_w else None)
+            g_cats[l + 1] = up_grads(l, du, cats[l + 1] if l < D - 1 else r)
+        # innermost down conv + ReLU
+        dy = ops.act_bwd(g_cats.pop(D), r, "relu")
+        g_d = down_grads(D - 1, dy, True, True)
+        for l in range(D - 2, -1, -1):
+            dn = lv[l][0]
+            dy = ops.instnorm_skip_bwd(g_d, g_cats.pop(l + 1), 0, ys[l], ss[l], db=dn.bias.grad if train_w else None,
+                                       slope=SLOPE)
+            g_d = down_grads(l, dy, False, l > 0 or ctx.needs_input_grad[0])
+        ctx.sv = None
+        return g_d, None, None
+
+
+###############################################################################
 # define_G / define_D (networks.py:119-203)
 ###############################################################################
 def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, init_type='normal',
@@ -965,8 +1176,13 @@ def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, in
         net = ResnetGenerator(input_nc, output_nc, ngf, norm_layer=norm_layer, use_dropout=use_dropout, n_blocks=9)
     elif netG == 'resnet_6blocks':
         net = ResnetGenerator(input_nc, output_nc, ngf, norm_layer=norm_layer, use_dropout=use_dropout, n_blocks=6)
-    elif netG in ('unet_128', 'unet_256'):
-        raise NotImplementedError('Generator [%s] is outside the HIP hot path (SURVEY §2)' % netG)
+    elif netG == 'unet_128':
+        net = UnetGenerator(input_nc, output_nc, 7, ngf, norm_layer=norm_layer, use_dropout=use_dropout)
+    elif netG == 'unet_256':
+        # the eight-level net runs (UnetGenerator(input_nc, output_nc, 8, ngf, norm_layer=...), tested at that depth);
+        # this name keeps its refusal here because the host suite holds define_G to it
+        raise NotImplementedError('Generator [%s] is not offered by define_G yet: construct '
+                                  'networks.UnetGenerator(input_nc, output_nc, 8, ngf, norm_layer) and init_net it' % netG)
     else:
         raise NotImplementedError('Generator model name [%s] is not recognized' % netG)
     return init_net(net, init_type, init_gain, gpu_ids)

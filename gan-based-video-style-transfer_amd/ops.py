@@ -695,6 +695,49 @@ def instnorm_act_bwd(ga, y, stats, act="relu", slope=0.0, db=None, accumulate_db
     return (dy, pl) if planes else dy
 
 
+def _skip_check(y, stats, cat, c0):
+    if y.dim() != 4 or cat.dim() != 4 or cat.shape[:3] != y.shape[:3]:
+        raise ValueError("instnorm_skip: y %s and cat %s must be NHWC over the same pixels" %
+                         (tuple(y.shape), tuple(cat.shape)))
+    N, H, W, C = y.shape
+    if stats is not None and tuple(stats.shape) != (N, C, 2):
+        raise ValueError("instnorm_skip: stats %s is not [N, C, 2] of y %s" % (tuple(stats.shape), tuple(y.shape)))
+    if c0 < 0 or c0 + C > cat.shape[-1]:
+        raise ValueError("instnorm_skip: channels [%d, %d) lie outside cat's %d" % (c0, c0 + C, cat.shape[-1]))
+    return N, H * W, C, cat.shape[-1]
+
+
+def instnorm_skip_fwd(y, stats, cat, c0, want_d=True, slope=0.2):
+    """The U-Net skip connection's forward (vst_instnorm_skip_fwd): z = IN(y) (stats None: z = y);
+    relu(z) goes into channels [c0, c0 + C) of the concatenation buffer cat, and d = lrelu(z) is returned
+    (want_d=False: None — the up norm's apply into its half of cat)."""
+    _dev_check(y, stats, cat)
+    N, HW, C, Cs = _skip_check(y, stats, cat, c0)
+    d = torch.empty_like(y) if want_d else None
+    _call("vst_instnorm_skip_fwd", _p(y), _p(stats), _p(d), _p(cat), N, HW, C, Cs, int(c0), float(slope), _stream())
+    return d
+
+
+def instnorm_skip_bwd(g_d, g_cat, c0, y, stats, db=None, accumulate_db=True, slope=0.2):
+    """Backward of instnorm_skip_fwd (vst_instnorm_skip_bwd): g = g_d * lrelu'(z) + g_cat[..., c0:c0 + C] *
+    relu'(z) (g_d None: the second term alone), then the IN backward (stats None: dy = g).  db (if given)
+    (+)= the per-channel sum of dy.  Returns dy."""
+    _dev_check(g_d, g_cat, y, stats, db)
+    N, HW, C, Cs = _skip_check(y, stats, g_cat, c0)
+    if g_d is not None and g_d.shape != y.shape:
+        raise ValueError("instnorm_skip_bwd: g_d %s does not match y %s" % (tuple(g_d.shape), tuple(y.shape)))
+    if db is not None and db.numel() != C:
+        raise ValueError("instnorm_skip_bwd: db has %d entries for %d channels" % (db.numel(), C))
+    dy = torch.empty_like(y)
+    ws = None
+    if stats is not None or db is not None:
+        nbytes = lib().vst_instnorm_skip_ws_bytes(N, HW, C)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=y.device)
+    _call("vst_instnorm_skip_bwd", _p(g_d), _p(g_cat), Cs, int(c0), _p(y), _p(stats), _p(dy), _p(db),
+          1 if accumulate_db else 0, _p(ws), N, HW, C, float(slope), _stream())
+    return dy
+
+
 def act_bwd(gy, y, act, slope=0.0):
     _dev_check(gy, y)
     dx = torch.empty_like(y)
@@ -1672,6 +1715,23 @@ def conv4s2_dgrad(dy, packs, cop, role="bwd"):
     y = torch.empty((N, 2 * Hd, 2 * Wd, cop), device=dy.device)
     _call("vst_interleave_phases_full", _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(y), N, Hd, Wd,
           cop, _stream())
+    return y
+
+
+def convT4s2_fwd(x, packs, bias, cop, act="none", role="fwd"):
+    """ConvTranspose2d(k=4, s=2, p=1) forward on NHWC x [N, H, W, Cx] -> [N, 2H, 2W, cop].  It is, operand for
+    operand, the data gradient of Conv2d(k=4, s=2, p=1) with the transposed weight [Ci][Co][4][4] read as that
+    conv's [Co][Ci]: packs = conv4s2_dgrad_phase_packs(weight).  Without a bias and an activation it is
+    conv4s2_dgrad itself (the grouped launch where that route takes the shape); with them the four 2x2 phase convs
+    carry them in their epilogues (each output pixel belongs to exactly one phase) ahead of the interleave."""
+    _dev_check(x, bias)
+    if bias is None and act == "none":
+        return conv4s2_dgrad(x, packs, cop, role=role)
+    N, H, W, _ = x.shape
+    outs = [conv2d_fwd(x, wp, bias, cop, 2, 2, 1, 1, "zero", act=act, role=role) for wp in packs]
+    y = torch.empty((N, 2 * H, 2 * W, cop), device=x.device)
+    _call("vst_interleave_phases_full", _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(y), N, H, W, cop,
+          _stream())
     return y
 
 

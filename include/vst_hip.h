@@ -34,6 +34,8 @@
  *   vst_instnorm_affine_*       nn.InstanceNorm2d(affine=True) (+ReLU, + ResidualBlock layer_strength
  *                               gate) of methods/learning-based/network.py:147-298 (FastStyleNet)
  *   vst_cond_instnorm_*         ConditionalBatchNorm2d (+ReLU) of network.py:120-217 (FastStyleNet, n_styles > 1)
+ *   vst_instnorm_skip_*         UnetSkipConnectionBlock's skip concatenation with its in-place LeakyReLU / ReLU
+ *                               (GAN-based networks.py:468-535; the unet_128 / unet_256 generators)
  *   vst_upsample2x_*            F.interpolate(scale_factor=2) in network.py:206-207
  *   vst_scaled_tanh_*           ConvTanh network.py:111-118
  *   vst_channel_normalize       fast_style_transfer.py:819-822 normalize (+ the fs_johnson.py:31 /255)
@@ -511,6 +513,25 @@ int vst_cond_instnorm_bwd(const float* gy, const float* x, const float* stats, c
                           const float* embed, const float* bn_weight, const float* bn_bias, float* dx,
                           float* dembed, float* dbn_weight, float* dbn_bias, float* dbias, float* ws, int N,
                           int HW, int C, int Cl, int S, int act, int accumulate, void* stream);
+/* U-Net skip connection (UnetSkipConnectionBlock.forward: cat([x, model(x)], 1) under the child's in-place
+ * LeakyReLU(slope) and the parent's in-place ReLU).  y [N][HW][C] NHWC; z = (y - mean) * rstd with stats from
+ * vst_instnorm_stats, or z = y when stats is NULL (the level below the outermost block, which has no norm).
+ * fwd: one read of y; writes d = lrelu(z) [N][HW][C] (the child down conv's input; skipped when d is NULL) and
+ * relu(z) into channels [c0, c0 + C) of cat [N][HW][Cs] — the skip half as every reader sees it, or with d NULL the
+ * up half relu(IN(u)).  The other channels of cat are not touched.
+ * bwd: g = g_d * (z > 0 ? 1 : slope) + g_s * (z > 0 ? 1 : 0), g_d [N][HW][C] (NULL: 0, the up norm's backward),
+ * g_s = channels [c0, c0 + C) of g_cat [N][HW][Cs] read in place; dy = rstd * (g - mean(g) - xhat * mean(g * xhat)),
+ * or dy = g when stats is NULL; db (may be NULL) (+)= the per-channel sum of dy (the bias gradient of the conv
+ * that made y), accumulated when accumulate_db != 0.  Partials fp64 in a fixed order, no atomics: two runs are
+ * bit-equal.  ws: vst_instnorm_skip_ws_bytes bytes (may be NULL when stats and db both are).
+ * C % 4 == 0, c0 % 4 == 0, Cs % 4 == 0, c0 + C <= Cs, C <= 1024: else VST_EUNSUPPORTED (ws_bytes returns 0);
+ * NULL pointers or non-positive sizes VST_EINVAL; nothing is launched in either case. */
+size_t vst_instnorm_skip_ws_bytes(int N, int HW, int C);
+int vst_instnorm_skip_fwd(const float* y, const float* stats, float* d, float* cat, int N, int HW, int C, int Cs,
+                          int c0, float slope, void* stream);
+int vst_instnorm_skip_bwd(const float* g_d, const float* g_cat, int Cs, int c0, const float* y, const float* stats,
+                          float* dy, float* db, int accumulate_db, float* ws, int N, int HW, int C, float slope,
+                          void* stream);
 /* Nearest 2x upsample of NHWC (Cs % 4 == 0): y [N][2H][2W][Cs]; backward sums each 2x2 block. */
 int vst_upsample2x_fwd(const float* x, float* y, int N, int H, int W, int Cs, void* stream);
 int vst_upsample2x_bwd(const float* gy, float* gx, int N, int H, int W, int Cs, void* stream);
