@@ -8,6 +8,12 @@
 // depend on the fp32 summation order), folded through LDS, and written per slice; a finalize
 // kernel folds the slices in a fixed order (deterministic).  The slice size adapts so every layer
 // launches ~512 blocks (64x64x256 res tensors and 256x256x64 outer tensors alike).
+//
+// That walk is written once (slice_partials): every family's partial kernel (plain, affine,
+// conditional, U-Net skip) hands it how a pixel row is loaded and what a pixel adds to the sums.
+// Affine and conditional IN are one operator, z = x * al + sh with per-(n, c) coefficients, and share
+// the mod_* bodies; they differ in the coefficient provider ({al, sh} for (n, c)) and in their
+// parameter-gradient kernels.
 #include "common.h"
 
 namespace vst {
@@ -40,15 +46,22 @@ static bool red_geom(int N, int HW, int C, RedGeom& g) {
 #define IN_UNROLL 4
 #endif
 
-// MODE 0: stats partials {sum x, sum x^2}; MODE 1: backward partials {sum g, sum g*xhat, sum xhat}
-template <int MODE>
-__global__ __launch_bounds__(NRED) void in_partial_k(const float* __restrict__ x,
-                                                     const float* __restrict__ gy,
-                                                     const float* __restrict__ stats,
-                                                     double* __restrict__ part, int HW, int C,
-                                                     int LP, int PG, int SP, int nsplit, int act,
-                                                     float slope) {
-  constexpr int NV = MODE == 0 ? 2 : 3;
+// d act(z) / dz from the pre-activation z (relu'(0) = 0, lrelu'(0) = slope)
+__device__ __forceinline__ float act_deriv(float z, int act, float slope) {
+  float d = 1.f;
+  if (act == VST_ACT_RELU) d = z > 0.f ? 1.f : 0.f;
+  else if (act == VST_ACT_LRELU) d = z > 0.f ? 1.f : slope;
+  return d;
+}
+
+// The slice walk of every partial kernel.  Block (z, n) owns pixels [z SP, min(HW, (z + 1) SP)) of image n;
+// thread t holds float4 column c4 = t % LP of pixel group pg = t / LP and takes rows p, p + PG, p + 2 PG, ...
+// in that order: load(p) fetches a row's operands, term(row, acc) adds them to the thread's NV x 4 fp64
+// sums.  UR rows' loads are issued together ahead of their (serial, order-preserving) accumulation.  The
+// groups are folded through LDS in the order q = 0 .. PG-1 and written to part[n][z][c][NV].
+template <int NV, class Load, class Term>
+__device__ __forceinline__ void slice_partials(Load load, Term term, double* __restrict__ part, int HW, int C,
+                                               int LP, int PG, int SP, int nsplit) {
   __shared__ double red[NV * 4][NRED];
   const int t = threadIdx.x, c4 = t % LP, pg = t / LP;
   const int n = blockIdx.y, z = blockIdx.x;
@@ -58,56 +71,17 @@ __global__ __launch_bounds__(NRED) void in_partial_k(const float* __restrict__ x
   for (int v = 0; v < NV; ++v)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[v][j] = 0.0;
-  float mean[4] = {0, 0, 0, 0}, rstd[4] = {0, 0, 0, 0};
-  if (MODE == 1) {
-    const float4 s0 = reinterpret_cast<const float4*>(stats)[((long)n * C + 4 * c4) / 2];
-    const float4 s1 = reinterpret_cast<const float4*>(stats)[((long)n * C + 4 * c4) / 2 + 1];
-    mean[0] = s0.x; rstd[0] = s0.y; mean[1] = s0.z; rstd[1] = s0.w;
-    mean[2] = s1.x; rstd[2] = s1.y; mean[3] = s1.z; rstd[3] = s1.w;
-  }
-  const float4* xb = reinterpret_cast<const float4*>(x) + (long)n * HW * LP + c4;
-  const float4* gb = reinterpret_cast<const float4*>(gy) + (long)n * HW * LP + c4;
-  // one pixel row's float4 (x, and g for MODE 1) into the fp64 partials
-  auto accum = [&](const float4 v, const float4 gv) {
-    const float xv[4] = {v.x, v.y, v.z, v.w};
-    if (MODE == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        acc[0][j] += xv[j];
-        acc[1][j] += (double)xv[j] * xv[j];
-      }
-    } else {
-      const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float xh = (xv[j] - mean[j]) * rstd[j];
-        float d = 1.f;
-        if (act == VST_ACT_RELU) d = xh > 0.f ? 1.f : 0.f;
-        else if (act == VST_ACT_LRELU) d = xh > 0.f ? 1.f : slope;
-        const float g = gg[j] * d;
-        acc[0][j] += g;
-        acc[1][j] += (double)g * xh;
-        acc[2][j] += xh;
-      }
-    }
-  };
-  // the thread's rows p, p + PG, p + 2 PG, ... accumulated in that order; UR rows' loads are
-  // issued together ahead of their (serial, order-preserving) fp64 accumulation
   constexpr int UR = IN_UNROLL;
   if (pg < PG) {
     int p = p0 + pg;
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     for (; p + (UR - 1) * PG < p1; p += UR * PG) {
-      float4 v[UR], gv[UR];
+      decltype(load(0L)) r[UR];
 #pragma unroll
-      for (int k = 0; k < UR; ++k) {
-        v[k] = xb[(long)(p + k * PG) * LP];
-        gv[k] = MODE == 1 ? gb[(long)(p + k * PG) * LP] : z4;
-      }
+      for (int k = 0; k < UR; ++k) r[k] = load((long)(p + k * PG));
 #pragma unroll
-      for (int k = 0; k < UR; ++k) accum(v[k], gv[k]);
+      for (int k = 0; k < UR; ++k) term(r[k], acc);
     }
-    for (; p < p1; p += PG) accum(xb[(long)p * LP], MODE == 1 ? gb[(long)p * LP] : z4);
+    for (; p < p1; p += PG) term(load((long)p), acc);
   }
 #pragma unroll
   for (int v = 0; v < NV; ++v)
@@ -115,7 +89,7 @@ __global__ __launch_bounds__(NRED) void in_partial_k(const float* __restrict__ x
     for (int j = 0; j < 4; ++j) red[v * 4 + j][t] = acc[v][j];
   __syncthreads();
   if (pg == 0) {
-    double out[NV][4];
+    double out[NV][4];  // all folded before any is stored: the 4 NV values go out as wide stores
 #pragma unroll
     for (int v = 0; v < NV; ++v)
 #pragma unroll
@@ -129,6 +103,52 @@ __global__ __launch_bounds__(NRED) void in_partial_k(const float* __restrict__ x
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int v = 0; v < NV; ++v) dst[j * NV + v] = out[v][j];
+  }
+}
+
+struct XG4 {  // a pixel row's float4 of the input and of the incoming gradient
+  float4 x, g;
+};
+
+// MODE 0: stats partials {sum x, sum x^2}; MODE 1: backward partials {sum g, sum g*xhat, sum xhat}
+template <int MODE>
+__global__ __launch_bounds__(NRED) void in_partial_k(const float* __restrict__ x,
+                                                     const float* __restrict__ gy,
+                                                     const float* __restrict__ stats,
+                                                     double* __restrict__ part, int HW, int C,
+                                                     int LP, int PG, int SP, int nsplit, int act,
+                                                     float slope) {
+  const int c4 = (int)threadIdx.x % LP, n = blockIdx.y;  // as the walk has them
+  const float4* xb = reinterpret_cast<const float4*>(x) + (long)n * HW * LP + c4;
+  if constexpr (MODE == 0) {
+    slice_partials<2>([=](long p) { return xb[p * LP]; },
+                      [](const float4 v, double(&acc)[2][4]) {
+                        const float xv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                          acc[0][j] += xv[j];
+                          acc[1][j] += (double)xv[j] * xv[j];
+                        }
+                      },
+                      part, HW, C, LP, PG, SP, nsplit);
+  } else {
+    const float4 s0 = reinterpret_cast<const float4*>(stats)[((long)n * C + 4 * c4) / 2];
+    const float4 s1 = reinterpret_cast<const float4*>(stats)[((long)n * C + 4 * c4) / 2 + 1];
+    const float mean[4] = {s0.x, s0.z, s1.x, s1.z}, rstd[4] = {s0.y, s0.w, s1.y, s1.w};
+    const float4* gb = reinterpret_cast<const float4*>(gy) + (long)n * HW * LP + c4;
+    slice_partials<3>([=](long p) { return XG4{xb[p * LP], gb[p * LP]}; },
+                      [&](const XG4& r, double(&acc)[3][4]) {
+                        const float xv[4] = {r.x.x, r.x.y, r.x.z, r.x.w}, gg[4] = {r.g.x, r.g.y, r.g.z, r.g.w};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                          const float xh = (xv[j] - mean[j]) * rstd[j];
+                          const float g = gg[j] * act_deriv(xh, act, slope);
+                          acc[0][j] += g;
+                          acc[1][j] += (double)g * xh;
+                          acc[2][j] += xh;
+                        }
+                      },
+                      part, HW, C, LP, PG, SP, nsplit);
   }
 }
 
@@ -203,8 +223,17 @@ __global__ void in_finalize_k(const double* __restrict__ part, float* __restrict
   stats[2 * idx + 1] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
-// coef[(n*C+c)] = {mean(g), mean(g*xhat)}; dbn[n*C+c] = sum_p dx = rstd*((sum g - HW*mean g)
-// - mean(g xhat)*sum xhat)  (the exact per-channel sum of the IN input gradient).
+// The backward finalize arithmetic of every family, from the folded a = {sum g, sum g*xhat, sum xhat, ..}:
+// k = {mean g, mean g*xhat} (the apply pass's coefficients); returns (sum g - HW*mean g) - mean(g xhat)*sum xhat,
+// which times the family's al is sum_p dx, the exact per-channel sum of the input gradient.
+template <int NV>
+__device__ __forceinline__ double bwd_coef(const double (&a)[NV], int HW, float2& k) {
+  const double mg = a[0] / HW, mgx = a[1] / HW;
+  k = make_float2((float)mg, (float)mgx);
+  return (a[0] - HW * mg) - mgx * a[2];
+}
+
+// coef[n*C+c] = {mean g, mean g*xhat}; dbn[n*C+c] = sum_p dx (al = rstd)
 template <int CPB>
 __global__ void in_bwd_finalize_k(const double* __restrict__ part, const float* __restrict__ stats,
                                   float2* __restrict__ coef, double* __restrict__ dbn, int N, int HW,
@@ -213,14 +242,9 @@ __global__ void in_bwd_finalize_k(const double* __restrict__ part, const float* 
   const int n = blockIdx.y;
   if (!fold_slices<3, CPB>(part, n, C, nsplit, a)) return;
   const int idx = n * C + blockIdx.x * CPB + (threadIdx.x % CPB);
-  const double mg = a[0] / HW, mgx = a[1] / HW;
-  coef[idx] = make_float2((float)mg, (float)mgx);
   const double rstd = stats[2 * idx + 1];
-  dbn[idx] = rstd * ((a[0] - HW * mg) - mgx * a[2]);
+  dbn[idx] = rstd * bwd_coef(a, HW, coef[idx]);
 }
-
-
-__device__ __forceinline__ void store_planes4(__bf16* __restrict__ pl, long pps, long e, float4 v);
 
 __global__ void in_apply_k(const float4* __restrict__ x, const float* __restrict__ stats,
                            const float4* __restrict__ res, float4* __restrict__ y, long total4,
@@ -249,19 +273,46 @@ __device__ __forceinline__ uint32_t bf16_pack2(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, b2));
 }
 
-// v's three bf16 planes (hi, mid, lo: the RNE split of nhwc_to_cp_planes_k / split8) at element e of planes
-// [3][pps] — the NHWC A-operand planes of an x6 data gradient that takes its A operand pre-split (APRE_BWD)
+// One step of the hi / mid / lo split (nhwc_to_cp_planes_k / split8): r's four values as RNE bf16, r left
+// holding what they did not take.  Three calls in a row give the three planes.
+__device__ __forceinline__ uint2 bf16_split4(float (&r)[4]) {
+  const uint32_t q0 = bf16_pack2(r[0], r[1]), q1 = bf16_pack2(r[2], r[3]);
+  r[0] -= __uint_as_float(q0 << 16);
+  r[1] -= __uint_as_float(q0 & 0xffff0000u);
+  r[2] -= __uint_as_float(q1 << 16);
+  r[3] -= __uint_as_float(q1 & 0xffff0000u);
+  return make_uint2(q0, q1);
+}
+
+// v's three bf16 planes at element e of planes [3][pps] — the NHWC A-operand planes of an x6 data gradient
+// that takes its A operand pre-split (APRE_BWD)
 __device__ __forceinline__ void store_planes4(__bf16* __restrict__ pl, long pps, long e, float4 v) {
   float r[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    const uint32_t q0 = bf16_pack2(r[0], r[1]), q1 = bf16_pack2(r[2], r[3]);
-    *reinterpret_cast<uint2*>(pl + p * pps + e) = make_uint2(q0, q1);
-    if (p < 2) {
-      r[0] -= __uint_as_float(q0 << 16);
-      r[1] -= __uint_as_float(q0 & 0xffff0000u);
-      r[2] -= __uint_as_float(q1 << 16);
-      r[3] -= __uint_as_float(q1 & 0xffff0000u);
+  for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(pl + p * pps + e) = bf16_split4(r);
+}
+
+// A block's 64-pixel x 64-channel LDS tile (pixels p0 .., channels c0 ..) out channel-major as three bf16 planes
+// [3][C][ld]: a thread takes 4 consecutive pixels of one channel row; the ragged last pixels of P go out as
+// 16-bit stores.  256 threads.
+__device__ __forceinline__ void tile_to_planes(const float (&tile)[64][65], __bf16* __restrict__ planes, long ld,
+                                               int C, long P, long p0, int c0) {
+  const long plane = (long)C * ld;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int idx = threadIdx.x + 256 * it, cr = idx >> 4, p4 = (idx & 15) * 4;
+    if (c0 + cr >= C || p0 + p4 >= P) continue;
+    float r[4] = {tile[p4][cr], tile[p4 + 1][cr], tile[p4 + 2][cr], tile[p4 + 3][cr]};
+    __bf16* dst = planes + (long)(c0 + cr) * ld + p0 + p4;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+      const uint2 q = bf16_split4(r);
+      if (p0 + p4 + 3 < P) {
+        *reinterpret_cast<uint2*>(dst + pl * plane) = q;
+      } else {
+        const uint16_t h[4] = {(uint16_t)q.x, (uint16_t)(q.x >> 16), (uint16_t)q.y, (uint16_t)(q.y >> 16)};
+        for (int e = 0; e < 4 && p0 + p4 + e < P; ++e) reinterpret_cast<uint16_t*>(dst + pl * plane)[e] = h[e];
+      }
     }
   }
 }
@@ -328,30 +379,7 @@ __global__ __launch_bounds__(256) void in_apply_cp_pad_k(const float* __restrict
   }
   __syncthreads();
   if (planes) {
-    const long plane = (long)C * ld;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int idx = t + 256 * it, cr = idx >> 4, p4 = (idx & 15) * 4;
-      if (c0 + cr >= C || p0 + p4 >= P) continue;
-      float r[4] = {tile[p4][cr], tile[p4 + 1][cr], tile[p4 + 2][cr], tile[p4 + 3][cr]};
-      __bf16* dst = planes + (long)(c0 + cr) * ld + p0 + p4;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-        const uint32_t q0 = bf16_pack2(r[0], r[1]), q1 = bf16_pack2(r[2], r[3]);
-        if (p0 + p4 + 3 < P) {
-          *reinterpret_cast<uint2*>(dst + pl * plane) = make_uint2(q0, q1);
-        } else {
-          const uint16_t h[4] = {(uint16_t)q0, (uint16_t)(q0 >> 16), (uint16_t)q1, (uint16_t)(q1 >> 16)};
-          for (int e = 0; e < 4 && p0 + p4 + e < P; ++e) reinterpret_cast<uint16_t*>(dst + pl * plane)[e] = h[e];
-        }
-        if (pl < 2) {
-          r[0] -= __uint_as_float(q0 << 16);
-          r[1] -= __uint_as_float(q0 & 0xffff0000u);
-          r[2] -= __uint_as_float(q1 << 16);
-          r[3] -= __uint_as_float(q1 & 0xffff0000u);
-        }
-      }
-    }
+    tile_to_planes(tile, planes, ld, C, P, p0, c0);
     return;
   }
 #pragma unroll
@@ -370,10 +398,7 @@ __global__ __launch_bounds__(256) void in_apply_cp_pad_k(const float* __restrict
 __device__ __forceinline__ float in_bwd1(float gy, float x, float mean, float rstd, float2 k, int act,
                                          float slope) {
   const float xh = (x - mean) * rstd;
-  float d = 1.f;
-  if (act == VST_ACT_RELU) d = xh > 0.f ? 1.f : 0.f;
-  else if (act == VST_ACT_LRELU) d = xh > 0.f ? 1.f : slope;
-  return rstd * (gy * d - k.x - xh * k.y);
+  return rstd * (gy * act_deriv(xh, act, slope) - k.x - xh * k.y);
 }
 
 // db[c] (+)= sum_n dbn[n][c] in a fixed order (the conv-bias gradient), by the first blocks of the
@@ -419,7 +444,6 @@ __global__ void in_bwd_apply_k(const float4* __restrict__ gy, const float4* __re
 // the RNE split of vst_weight_split / nhwc_to_cp_planes_k) through a 64-pixel x 64-channel LDS
 // transpose tile — the conv below the IN consumes dx both ways, so the plane copy's extra read of dx
 // is gone.  grid (ceil(P / 64), ceil(C / 64)), 256 threads.
-
 __global__ __launch_bounds__(256) void in_bwd_apply_planes_k(const float* __restrict__ gy, const float* __restrict__ x,
                                                               const float* __restrict__ stats,
                                                               const float2* __restrict__ coef, float* __restrict__ dx,
@@ -458,30 +482,7 @@ __global__ __launch_bounds__(256) void in_bwd_apply_planes_k(const float* __rest
     tile[pr][c4 + 3] = o.w;
   }
   __syncthreads();
-  const long plane = (long)C * ldp;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int idx = t + 256 * it, cr = idx >> 4, p4 = (idx & 15) * 4;
-    if (c0 + cr >= C || p0 + p4 >= P) continue;
-    float r[4] = {tile[p4][cr], tile[p4 + 1][cr], tile[p4 + 2][cr], tile[p4 + 3][cr]};
-    __bf16* dst = planes + (long)(c0 + cr) * ldp + p0 + p4;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      const uint32_t q0 = bf16_pack2(r[0], r[1]), q1 = bf16_pack2(r[2], r[3]);
-      if (p0 + p4 + 3 < P) {
-        *reinterpret_cast<uint2*>(dst + pl * plane) = make_uint2(q0, q1);
-      } else {
-        const uint16_t h[4] = {(uint16_t)q0, (uint16_t)(q0 >> 16), (uint16_t)q1, (uint16_t)(q1 >> 16)};
-        for (int e = 0; e < 4 && p0 + p4 + e < P; ++e) reinterpret_cast<uint16_t*>(dst + pl * plane)[e] = h[e];
-      }
-      if (pl < 2) {
-        r[0] -= __uint_as_float(q0 << 16);
-        r[1] -= __uint_as_float(q0 & 0xffff0000u);
-        r[2] -= __uint_as_float(q1 << 16);
-        r[3] -= __uint_as_float(q1 & 0xffff0000u);
-      }
-    }
-  }
+  tile_to_planes(tile, planes, ldp, C, P, p0, c0);
 }
 
 __global__ void act_bwd_k(const float* __restrict__ gy, const float* __restrict__ y,
@@ -527,38 +528,60 @@ __global__ void chsum_final_k(const double* __restrict__ part, float* __restrict
   db[c] = accumulate ? db[c] + (float)s[0] : (float)s[0];
 }
 
-
-// ---- affine InstanceNorm (nn.InstanceNorm2d(affine=True), learning-based network.py:147-261) ---
-// y = s * act(gamma[c] * xhat + beta[c]) + residual, xhat = (x - mean) * rstd, computed as ATen's
-// CPU batch-norm transform does: z = x * alpha + (beta - mean * alpha), alpha = rstd * gamma.
+// ---- modulated InstanceNorm: y = s * act(z) + residual, z = x * al + sh ---------------------------------------
+// al = rstd * A, sh = B - mean * al with a per-(n, c) scale A and shift B; xhat = (x - mean) * rstd.  Backward:
+// gz = s * gy * act'(z), dx = al * (gz - mean gz - xhat * mean(gz * xhat)).  A family is a coefficient provider
+// (a small struct passed by value whose operator()(n, c) returns {al, sh}, or TabCoef over a table it wrote) handed
+// to the three bodies below, its own finalize (what it keeps of the folded sums) and its own parameter-gradient
+// kernel.
 // s = 1, or the ResidualBlock gate s = 2|u| / (1 + |u|), u = gate_mult * gate[0]
-// (network.py:241-245 layer_strength).
+// (learning-based network.py:241-245 layer_strength).
 __device__ __forceinline__ float gate_scale(const float* gate, float mult) {
   if (!gate) return 1.f;
   const float u = fabsf(mult * gate[0]);
   return 2.f * u / (1.f + u);
 }
 
-__global__ void in_aff_apply_k(const float4* __restrict__ x, const float* __restrict__ stats,
-                               const float* __restrict__ gamma, const float* __restrict__ beta,
-                               const float* __restrict__ gate, float gate_mult,
-                               const float4* __restrict__ res, float4* __restrict__ y, long total4,
-                               int HW, int C4, int act, float slope) {
+// a thread's four channels' {al, sh}
+template <class Coef>
+__device__ __forceinline__ void coef4(Coef coef, int n, int c4, float (&al)[4], float (&sh)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float2 k = coef(n, 4 * c4 + j);
+    al[j] = k.x;
+    sh[j] = k.y;
+  }
+}
+
+// The provider of a family that tabulates its coefficients, tab[n*C + c] = {al, sh}: a thread's four as two
+// float4 loads (the apply passes, which would otherwise gather per element).
+struct TabCoef {
+  const float2* tab;
+  int C;
+};
+__device__ __forceinline__ void coef4(TabCoef t, int n, int c4, float (&al)[4], float (&sh)[4]) {
+  const float4* p = reinterpret_cast<const float4*>(t.tab + (long)n * t.C + 4 * c4);
+  const float4 t0 = p[0], t1 = p[1];  // {al0, sh0, al1, sh1}, {al2, sh2, al3, sh3}
+  al[0] = t0.x; sh[0] = t0.y; al[1] = t0.z; sh[1] = t0.w;
+  al[2] = t1.x; sh[2] = t1.y; al[3] = t1.z; sh[3] = t1.w;
+}
+
+template <class Coef>
+__device__ __forceinline__ void mod_apply(const float4* __restrict__ x, Coef coef, const float* __restrict__ gate,
+                                          float gate_mult, const float4* __restrict__ res, float4* __restrict__ y,
+                                          long total4, int HW, int C4, int act, float slope) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total4) return;
   const int c4 = i % C4;
   const int n = (i / C4) / HW;
   const float sc = gate_scale(gate, gate_mult);
-  const float* st = stats + ((long)n * C4 + c4) * 8;
   const float4 v = x[i];
   const float xv[4] = {v.x, v.y, v.z, v.w};
-  float o[4];
+  float al[4], sh[4], o[4];
+  coef4(coef, n, c4, al, sh);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int c = 4 * c4 + j;
-    const float al = st[2 * j + 1] * gamma[c];
-    const float be = beta[c] - st[2 * j] * al;
-    float z = apply_act(xv[j] * al + be, act, slope);
+    const float z = apply_act(xv[j] * al[j] + sh[j], act, slope);
     o[j] = gate ? sc * z : z;
   }
   float4 r = make_float4(o[0], o[1], o[2], o[3]);
@@ -566,8 +589,96 @@ __global__ void in_aff_apply_k(const float4* __restrict__ x, const float* __rest
   y[i] = r;
 }
 
-// backward partials per (n, c) slice: {sum gz, sum gz*xhat, sum xhat, sum gy*a},
-// gz = s * gy * act'(z), a = act(z) (the gate-input activation)
+// backward partials per (n, c) slice: {sum gz, sum gz*xhat, sum xhat} and, NV = 4 (the gate's gradient),
+// sum gy*act(z).  Each thread fetches its four channels' coefficients once, ahead of its pixel rows.
+// The activation derivative is spelled gz = sc * gy * d, d = act'(z) (the affine kernels' spelling; the
+// conditional kernels selected gy or 0, which differs only in the sign of a zero); d's value on z <= 0 is
+// uniform and taken once per thread, so an element costs a compare and a select, no branch on act.
+template <int NV, class Coef>
+__device__ __forceinline__ void mod_partial(const float* __restrict__ x, const float* __restrict__ gy,
+                                            const float* __restrict__ stats, Coef coef, float sc,
+                                            double* __restrict__ part, int HW, int C, int LP, int PG, int SP,
+                                            int nsplit, int act, float slope) {
+  const int c4 = (int)threadIdx.x % LP, n = blockIdx.y;  // as the walk has them
+  float mean[4], rstd[4], al[4], sh[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = 4 * c4 + j;
+    mean[j] = stats[2 * ((long)n * C + c)];
+    rstd[j] = stats[2 * ((long)n * C + c) + 1];
+  }
+  coef4(coef, n, c4, al, sh);
+  const float dneg = act_deriv(-1.f, act, slope);  // act'(z <= 0), once per thread; act'(z > 0) = 1
+  const float4* xb = reinterpret_cast<const float4*>(x) + (long)n * HW * LP + c4;
+  const float4* gb = reinterpret_cast<const float4*>(gy) + (long)n * HW * LP + c4;
+  slice_partials<NV>([=](long p) { return XG4{xb[p * LP], gb[p * LP]}; },
+                     [&](const XG4& r, double(&acc)[NV][4]) {
+                       const float xv[4] = {r.x.x, r.x.y, r.x.z, r.x.w}, gg[4] = {r.g.x, r.g.y, r.g.z, r.g.w};
+#pragma unroll
+                       for (int j = 0; j < 4; ++j) {
+                         const float xh = (xv[j] - mean[j]) * rstd[j];
+                         const float zz = xv[j] * al[j] + sh[j];
+                         const float g = sc * gg[j] * (zz > 0.f ? 1.f : dneg);
+                         acc[0][j] += g;
+                         acc[1][j] += (double)g * xh;
+                         acc[2][j] += xh;
+                         if constexpr (NV == 4) acc[3][j] += (double)gg[j] * apply_act(zz, act, slope);
+                       }
+                     },
+                     part, HW, C, LP, PG, SP, nsplit);
+}
+
+// kcoef[n*C+c] = {mean gz, mean gz*xhat} (bwd_coef)
+template <class Coef>
+__device__ __forceinline__ void mod_bwd_apply(const float4* __restrict__ gy, const float4* __restrict__ x,
+                                              const float* __restrict__ stats, Coef coef, float sc,
+                                              const float2* __restrict__ kcoef, float4* __restrict__ dx,
+                                              long total4, int HW, int C4, int act, float slope) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total4) return;
+  const int c4 = i % C4;
+  const int n = (i / C4) / HW;
+  const long q = ((long)n * C4 + c4) * 2;
+  const float4 g4 = gy[i], v = x[i];
+  const float4 s0 = reinterpret_cast<const float4*>(stats)[q], s1 = reinterpret_cast<const float4*>(stats)[q + 1];
+  const float4 k0 = reinterpret_cast<const float4*>(kcoef)[q], k1 = reinterpret_cast<const float4*>(kcoef)[q + 1];
+  const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, xv[4] = {v.x, v.y, v.z, v.w};
+  const float mean[4] = {s0.x, s0.z, s1.x, s1.z}, rstd[4] = {s0.y, s0.w, s1.y, s1.w};
+  const float kg[4] = {k0.x, k0.z, k1.x, k1.z}, kx[4] = {k0.y, k0.w, k1.y, k1.w};
+  float al[4], sh[4], o[4];
+  coef4(coef, n, c4, al, sh);
+  const float dneg = act_deriv(-1.f, act, slope);  // act'(z <= 0); act'(z > 0) = 1
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float zz = xv[j] * al[j] + sh[j];
+    const float g = sc * gg[j] * (zz > 0.f ? 1.f : dneg);
+    const float xh = (xv[j] - mean[j]) * rstd[j];
+    o[j] = al[j] * (g - kg[j] - xh * kx[j]);
+  }
+  dx[i] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// ---- affine InstanceNorm (nn.InstanceNorm2d(affine=True), learning-based network.py:147-261) ---
+// A = gamma[c], B = beta[c]: z = x * alpha + (beta - mean * alpha), alpha = rstd * gamma, as ATen's CPU
+// batch-norm transform computes it.  No coefficient table: every pass takes {al, sh} from stats / gamma / beta.
+struct AffCoef {
+  const float *stats, *gamma, *beta;
+  int C;
+  __device__ float2 operator()(int n, int c) const {
+    const float mean = stats[2 * ((long)n * C + c)], rstd = stats[2 * ((long)n * C + c) + 1];
+    const float al = rstd * gamma[c];
+    return make_float2(al, beta[c] - mean * al);
+  }
+};
+
+__global__ void in_aff_apply_k(const float4* __restrict__ x, const float* __restrict__ stats,
+                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                               const float* __restrict__ gate, float gate_mult,
+                               const float4* __restrict__ res, float4* __restrict__ y, long total4,
+                               int HW, int C4, int act, float slope) {
+  mod_apply(x, AffCoef{stats, gamma, beta, 4 * C4}, gate, gate_mult, res, y, total4, HW, C4, act, slope);
+}
+
 __global__ __launch_bounds__(NRED) void in_aff_partial_k(const float* __restrict__ x,
                                                          const float* __restrict__ gy,
                                                          const float* __restrict__ stats,
@@ -577,64 +688,8 @@ __global__ __launch_bounds__(NRED) void in_aff_partial_k(const float* __restrict
                                                          double* __restrict__ part, int HW, int C,
                                                          int LP, int PG, int SP, int nsplit, int act,
                                                          float slope) {
-  constexpr int NV = 4;
-  __shared__ double red[NV * 4][NRED];
-  const int t = threadIdx.x, c4 = t % LP, pg = t / LP;
-  const int n = blockIdx.y, z = blockIdx.x;
-  const int p0 = z * SP, p1 = min(HW, p0 + SP);
-  const float sc = gate_scale(gate, gate_mult);
-  double acc[NV][4];
-#pragma unroll
-  for (int v = 0; v < NV; ++v)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[v][j] = 0.0;
-  float mean[4], rstd[4], ga[4], be[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int c = 4 * c4 + j < C ? 4 * c4 + j : 0;
-    mean[j] = stats[2 * ((long)n * C + c)];
-    rstd[j] = stats[2 * ((long)n * C + c) + 1];
-    ga[j] = gamma[c];
-    be[j] = beta[c];
-  }
-  const float4* xb = reinterpret_cast<const float4*>(x) + (long)n * HW * LP + c4;
-  const float4* gb = reinterpret_cast<const float4*>(gy) + (long)n * HW * LP + c4;
-  for (int p = p0 + pg; pg < PG && p < p1; p += PG) {
-    const float4 v = xb[(long)p * LP];
-    const float4 gv = gb[(long)p * LP];
-    const float xv[4] = {v.x, v.y, v.z, v.w};
-    const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xh = (xv[j] - mean[j]) * rstd[j];
-      const float al = rstd[j] * ga[j];
-      const float zz = xv[j] * al + (be[j] - mean[j] * al);
-      float d = 1.f;
-      if (act == VST_ACT_RELU) d = zz > 0.f ? 1.f : 0.f;
-      else if (act == VST_ACT_LRELU) d = zz > 0.f ? 1.f : slope;
-      const float g = sc * gg[j] * d;
-      acc[0][j] += g;
-      acc[1][j] += (double)g * xh;
-      acc[2][j] += xh;
-      acc[3][j] += (double)gg[j] * apply_act(zz, act, slope);
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < NV; ++v)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[v * 4 + j][t] = acc[v][j];
-  __syncthreads();
-  if (pg == 0) {
-    double* dst = part + (((long)n * nsplit + z) * C + 4 * c4) * NV;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        double s = 0.0;
-        for (int q = 0; q < PG; ++q) s += red[v * 4 + j][q * LP + c4];
-        dst[j * NV + v] = s;
-      }
-  }
+  mod_partial<4>(x, gy, stats, AffCoef{stats, gamma, beta, C}, gate_scale(gate, gate_mult), part, HW, C, LP, PG, SP,
+                 nsplit, act, slope);
 }
 
 // coef[n*C+c] = {mean gz, mean gz*xhat}; sums[n*C+c] = {sum gz, sum gz*xhat, sum gy*a, dbias}
@@ -646,13 +701,11 @@ __global__ void in_aff_finalize_k(const double* __restrict__ part, const float* 
   if (!fold_slices<4>(part, n, C, nsplit, a)) return;
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int idx = n * C + c;
-  const double mg = a[0] / HW, mgx = a[1] / HW;
-  coef[idx] = make_float2((float)mg, (float)mgx);
   const double rstd = stats[2 * idx + 1];
   sums[4 * idx + 0] = a[0];
   sums[4 * idx + 1] = a[1];
   sums[4 * idx + 2] = a[3];
-  sums[4 * idx + 3] = rstd * gamma[c] * ((a[0] - HW * mg) - mgx * a[2]);
+  sums[4 * idx + 3] = rstd * gamma[c] * bwd_coef(a, HW, coef[idx]);
 }
 
 // one block: dgamma/dbeta/dbias per channel (sum over n, fixed order) and the gate gradient
@@ -695,32 +748,9 @@ __global__ void in_aff_bwd_apply_k(const float4* __restrict__ gy, const float4* 
                                    float gate_mult, const float2* __restrict__ coef,
                                    float4* __restrict__ dx, long total4, int HW, int C4, int act,
                                    float slope) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total4) return;
-  const int c4 = i % C4;
-  const int n = (i / C4) / HW;
-  const float sc = gate_scale(gate, gate_mult);
-  const long nc = (long)n * C4 * 4 + 4 * c4;
-  const float4 g4 = gy[i], v = x[i];
-  const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, xv[4] = {v.x, v.y, v.z, v.w};
-  float o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int c = 4 * c4 + j;
-    const float mean = stats[2 * (nc + j)], rstd = stats[2 * (nc + j) + 1];
-    const float al = rstd * gamma[c];
-    const float zz = xv[j] * al + (beta[c] - mean * al);
-    float d = 1.f;
-    if (act == VST_ACT_RELU) d = zz > 0.f ? 1.f : 0.f;
-    else if (act == VST_ACT_LRELU) d = zz > 0.f ? 1.f : slope;
-    const float g = sc * gg[j] * d;
-    const float xh = (xv[j] - mean) * rstd;
-    const float2 k = coef[nc + j];
-    o[j] = al * (g - k.x - xh * k.y);
-  }
-  dx[i] = make_float4(o[0], o[1], o[2], o[3]);
+  mod_bwd_apply(gy, x, stats, AffCoef{stats, gamma, beta, 4 * C4}, gate_scale(gate, gate_mult), coef, dx, total4, HW,
+                C4, act, slope);
 }
-
 
 // ---- conditional InstanceNorm (ConditionalBatchNorm2d, learning-based network.py:120-145) -------
 // y = act(ge * (w * xhat + b) + be) with {ge, be} = the halves of embedding row sid[n], {w, b} the inner
@@ -744,88 +774,37 @@ __device__ __forceinline__ float2 cond_alsh(const float* __restrict__ stats, con
   return make_float2(al, B - mean * al);
 }
 
+struct CondCoef {  // gathered from the embedding row (the partial and finalize passes: once per thread)
+  const float* stats;
+  const int* sid;
+  const float *embed, *bnw, *bnb;
+  int C, Cl, S;
+  __device__ float2 operator()(int n, int c) const { return cond_alsh(stats, sid, embed, bnw, bnb, n, c, C, Cl, S); }
+};
+
 // tab[n*C + c] = {al, sh}: the forward apply's coefficients, one thread per (n, c)
 __global__ void cond_coef_k(const float* __restrict__ stats, const int* __restrict__ sid,
                             const float* __restrict__ embed, const float* __restrict__ bnw,
                             const float* __restrict__ bnb, float2* __restrict__ tab, int N, int C, int Cl, int S) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N * C) return;
-  tab[i] = cond_alsh(stats, sid, embed, bnw, bnb, i / C, i % C, C, Cl, S);
+  tab[i] = CondCoef{stats, sid, embed, bnw, bnb, C, Cl, S}(i / C, i % C);
 }
 
 __global__ void cond_apply_k(const float4* __restrict__ x, const float4* __restrict__ tab, float4* __restrict__ y,
                              long total4, int HW, int C4, int act) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total4) return;
-  const int c4 = i % C4;
-  const int n = (i / C4) / HW;
-  const float4* t = tab + ((long)n * C4 + c4) * 2;
-  const float4 t0 = t[0], t1 = t[1], v = x[i];  // {al0, sh0, al1, sh1}, {al2, sh2, al3, sh3}
-  y[i] = make_float4(apply_act(v.x * t0.x + t0.y, act, 0.f), apply_act(v.y * t0.z + t0.w, act, 0.f),
-                     apply_act(v.z * t1.x + t1.y, act, 0.f), apply_act(v.w * t1.z + t1.w, act, 0.f));
+  mod_apply(x, TabCoef{reinterpret_cast<const float2*>(tab), 4 * C4}, nullptr, 0.f, nullptr, y, total4, HW, C4, act,
+            0.f);
 }
 
-// backward partials per (n, c) slice: {sum gz, sum gz*xhat, sum xhat}, gz = gy * act'(z).  Each thread gathers
-// its four channels' coefficients once, ahead of its pixel rows.
 __global__ __launch_bounds__(NRED) void cond_partial_k(const float* __restrict__ x, const float* __restrict__ gy,
                                                        const float* __restrict__ stats, const int* __restrict__ sid,
                                                        const float* __restrict__ embed,
                                                        const float* __restrict__ bnw, const float* __restrict__ bnb,
                                                        double* __restrict__ part, int HW, int C, int Cl, int S,
                                                        int LP, int PG, int SP, int nsplit, int act) {
-  constexpr int NV = 3;
-  __shared__ double red[NV * 4][NRED];
-  const int t = threadIdx.x, c4 = t % LP, pg = t / LP;
-  const int n = blockIdx.y, z = blockIdx.x;
-  const int p0 = z * SP, p1 = min(HW, p0 + SP);
-  double acc[NV][4];
-#pragma unroll
-  for (int v = 0; v < NV; ++v)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[v][j] = 0.0;
-  float mean[4], rstd[4], al[4], sh[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int c = 4 * c4 + j;
-    mean[j] = stats[2 * ((long)n * C + c)];
-    rstd[j] = stats[2 * ((long)n * C + c) + 1];
-    const float2 k = cond_alsh(stats, sid, embed, bnw, bnb, n, c, C, Cl, S);
-    al[j] = k.x;
-    sh[j] = k.y;
-  }
-  const float4* xb = reinterpret_cast<const float4*>(x) + (long)n * HW * LP + c4;
-  const float4* gb = reinterpret_cast<const float4*>(gy) + (long)n * HW * LP + c4;
-  for (int p = p0 + pg; pg < PG && p < p1; p += PG) {
-    const float4 v = xb[(long)p * LP];
-    const float4 gv = gb[(long)p * LP];
-    const float xv[4] = {v.x, v.y, v.z, v.w};
-    const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xh = (xv[j] - mean[j]) * rstd[j];
-      const float zz = xv[j] * al[j] + sh[j];
-      const float g = (act == VST_ACT_RELU && !(zz > 0.f)) ? 0.f : gg[j];
-      acc[0][j] += g;
-      acc[1][j] += (double)g * xh;
-      acc[2][j] += xh;
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < NV; ++v)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[v * 4 + j][t] = acc[v][j];
-  __syncthreads();
-  if (pg == 0) {
-    double* dst = part + (((long)n * nsplit + z) * C + 4 * c4) * NV;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        double s = 0.0;
-        for (int q = 0; q < PG; ++q) s += red[v * 4 + j][q * LP + c4];
-        dst[j * NV + v] = s;
-      }
-  }
+  mod_partial<3>(x, gy, stats, CondCoef{stats, sid, embed, bnw, bnb, C, Cl, S}, 1.f, part, HW, C, LP, PG, SP, nsplit,
+                 act, 0.f);
 }
 
 // tab[n*C+c] = {al, sh}, coef[n*C+c] = {mean gz, mean gz*xhat} for the backward apply;
@@ -840,13 +819,11 @@ __global__ void cond_finalize_k(const double* __restrict__ part, const float* __
   if (!fold_slices<3>(part, n, C, nsplit, a)) return;
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int idx = n * C + c;
-  const float2 k = cond_alsh(stats, sid, embed, bnw, bnb, n, c, C, Cl, S);
-  const double mg = a[0] / HW, mgx = a[1] / HW;
+  const float2 k = CondCoef{stats, sid, embed, bnw, bnb, C, Cl, S}(n, c);
   tab[idx] = k;
-  coef[idx] = make_float2((float)mg, (float)mgx);
   sums[3 * idx + 0] = a[0];
   sums[3 * idx + 1] = a[1];
-  sums[3 * idx + 2] = (double)k.x * ((a[0] - HW * mg) - mgx * a[2]);
+  sums[3 * idx + 2] = (double)k.x * bwd_coef(a, HW, coef[idx]);
 }
 
 // one block, a thread per real channel: the table rows style by style (samples in index order, every row
@@ -889,28 +866,9 @@ __global__ void cond_bwd_apply_k(const float4* __restrict__ gy, const float4* __
                                  const float4* __restrict__ stats, const float4* __restrict__ tab,
                                  const float4* __restrict__ coef, float4* __restrict__ dx, long total4, int HW,
                                  int C4, int act) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total4) return;
-  const int c4 = i % C4;
-  const int n = (i / C4) / HW;
-  const long q = ((long)n * C4 + c4) * 2;
-  const float4 g4 = gy[i], v = x[i];
-  const float4 s0 = stats[q], s1 = stats[q + 1], t0 = tab[q], t1 = tab[q + 1], k0 = coef[q], k1 = coef[q + 1];
-  const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, xv[4] = {v.x, v.y, v.z, v.w};
-  const float mean[4] = {s0.x, s0.z, s1.x, s1.z}, rstd[4] = {s0.y, s0.w, s1.y, s1.w};
-  const float al[4] = {t0.x, t0.z, t1.x, t1.z}, sh[4] = {t0.y, t0.w, t1.y, t1.w};
-  const float kg[4] = {k0.x, k0.z, k1.x, k1.z}, kx[4] = {k0.y, k0.w, k1.y, k1.w};
-  float o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float zz = xv[j] * al[j] + sh[j];
-    const float g = (act == VST_ACT_RELU && !(zz > 0.f)) ? 0.f : gg[j];
-    const float xh = (xv[j] - mean[j]) * rstd[j];
-    o[j] = al[j] * (g - kg[j] - xh * kx[j]);
-  }
-  dx[i] = make_float4(o[0], o[1], o[2], o[3]);
+  mod_bwd_apply(gy, x, reinterpret_cast<const float*>(stats), TabCoef{reinterpret_cast<const float2*>(tab), 4 * C4},
+                1.f, reinterpret_cast<const float2*>(coef), dx, total4, HW, C4, act, 0.f);
 }
-
 
 // ---- running statistics (nn.InstanceNorm2d(track_running_stats=True), StarGAN model.py:13-16) ---
 // ATen instance_norm: batch_norm over (1, N*C, HW) with the running buffers repeated N times, then
@@ -992,69 +950,35 @@ __global__ __launch_bounds__(NRED) void skip_partial_k(const float* __restrict__
                                                        double* __restrict__ part, int HW, int C, int Cs, int c0,
                                                        int LP, int PG, int SP, int nsplit, float slope) {
   constexpr int NV = STATS ? 3 : 1;
-  __shared__ double red[NV * 4][NRED];
-  const int t = threadIdx.x, c4 = t % LP, pg = t / LP;
-  const int n = blockIdx.y, z = blockIdx.x;
-  const int p0 = z * SP, p1 = min(HW, p0 + SP);
-  double acc[NV][4];
-#pragma unroll
-  for (int v = 0; v < NV; ++v)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[v][j] = 0.0;
+  struct Row {
+    float4 y, gd, gs;
+  };
+  const int c4 = (int)threadIdx.x % LP, n = blockIdx.y;  // as the walk has them
   const float4* yb = reinterpret_cast<const float4*>(y) + (long)n * HW * LP + c4;
   const float4* db = gd ? reinterpret_cast<const float4*>(gd) + (long)n * HW * LP + c4 : nullptr;
   const float* sb = gcat + (long)n * HW * Cs + c0 + 4 * c4;
   const long nc4 = (long)n * LP + c4;
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  auto accum = [&](float4 v, const float4 a, const float4 b) {
-    if (STATS) skip_z4(v, stats, nc4);
-    const float zz[4] = {v.x, v.y, v.z, v.w};
-    const float ga[4] = {a.x, a.y, a.z, a.w}, gb[4] = {b.x, b.y, b.z, b.w};
+  slice_partials<NV>(
+      [=](long p) {
+        return Row{yb[p * LP], db ? db[p * LP] : make_float4(0.f, 0.f, 0.f, 0.f),
+                   *reinterpret_cast<const float4*>(sb + p * Cs)};
+      },
+      [=](const Row& r, double(&acc)[NV][4]) {
+        float4 v = r.y;
+        if (STATS) skip_z4(v, stats, nc4);
+        const float zz[4] = {v.x, v.y, v.z, v.w};
+        const float ga[4] = {r.gd.x, r.gd.y, r.gd.z, r.gd.w}, gb[4] = {r.gs.x, r.gs.y, r.gs.z, r.gs.w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float g = skip_g(ga[j], gb[j], zz[j], slope);
-      acc[0][j] += g;
-      if (STATS) {
-        acc[1][j] += (double)g * zz[j];
-        acc[2][j] += zz[j];
-      }
-    }
-  };
-  // rows p, p + PG, ... in that order; UR rows' loads issued ahead of their serial fp64 accumulation
-  constexpr int UR = IN_UNROLL;
-  if (pg < PG) {
-    int p = p0 + pg;
-    for (; p + (UR - 1) * PG < p1; p += UR * PG) {
-      float4 v[UR], a[UR], b[UR];
-#pragma unroll
-      for (int k = 0; k < UR; ++k) {
-        const long q = p + k * PG;
-        v[k] = yb[q * LP];
-        a[k] = db ? db[q * LP] : z4;
-        b[k] = *reinterpret_cast<const float4*>(sb + q * Cs);
-      }
-#pragma unroll
-      for (int k = 0; k < UR; ++k) accum(v[k], a[k], b[k]);
-    }
-    for (; p < p1; p += PG)
-      accum(yb[(long)p * LP], db ? db[(long)p * LP] : z4, *reinterpret_cast<const float4*>(sb + (long)p * Cs));
-  }
-#pragma unroll
-  for (int v = 0; v < NV; ++v)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[v * 4 + j][t] = acc[v][j];
-  __syncthreads();
-  if (pg == 0) {
-    double* dst = part + (((long)n * nsplit + z) * C + 4 * c4) * NV;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        double s = 0.0;
-        for (int q = 0; q < PG; ++q) s += red[v * 4 + j][q * LP + c4];
-        dst[j * NV + v] = s;
-      }
-  }
+        for (int j = 0; j < 4; ++j) {
+          const float g = skip_g(ga[j], gb[j], zz[j], slope);
+          acc[0][j] += g;
+          if constexpr (STATS) {
+            acc[1][j] += (double)g * zz[j];
+            acc[2][j] += zz[j];
+          }
+        }
+      },
+      part, HW, C, LP, PG, SP, nsplit);
 }
 
 // without stats the slices hold the gradient's sums alone: dbn[n][c] = sum_z part[n][z][c]
@@ -1103,13 +1027,42 @@ __global__ void skip_bwd_apply_k(const float4* __restrict__ gd, const float* __r
 
 using namespace vst;
 
+// A backward workspace and its size: slice partials [N][nsplit][C][nv] fp64 | ntab float2 tables [N][C] (the
+// {mean g, mean g*xhat} coefficients last) | nsum fp64 sums per (n, c).
+struct BwdWs {
+  double* part;
+  float2* tab;
+  double* sums;
+  size_t bytes;
+  BwdWs(float* ws, int N, int nsplit, int C, int nv, int ntab, int nsum) {
+    const size_t otab = (size_t)N * nsplit * C * nv * sizeof(double), osum = otab + (size_t)N * C * ntab * sizeof(float2);
+    part = reinterpret_cast<double*>(ws);
+    tab = reinterpret_cast<float2*>(reinterpret_cast<char*>(ws) + otab);
+    sums = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + osum);
+    bytes = osum + (size_t)N * C * nsum * sizeof(double) + 256;
+  }
+};
+
+// a finalize kernel's <4> / <16> instantiation at the fin_cpb width: grid (C / CPB, N), 256 threads
+template <class K4, class K16, class... Args>
+static void launch_fin(K4 k4, K16 k16, int C, int N, int nsplit, hipStream_t s, Args... args) {
+  if (fin_cpb(C, N, nsplit) == 4)
+    hipLaunchKernelGGL(k4, dim3(ceil_div(C, 4), N), dim3(256), 0, s, args...);
+  else
+    hipLaunchKernelGGL(k16, dim3(ceil_div(C, 16), N), dim3(256), 0, s, args...);
+}
+
+extern "C" size_t vst_instnorm_ws_bytes(int N, int HW, int C) {
+  RedGeom g;
+  if (!red_geom(N, HW, C, g)) return 0;
+  return BwdWs(nullptr, N, g.nsplit, C, 3, 1, 1).bytes;
+}
+
 // ---- U-Net skip connection ------------------------------------------------------------------------
 // workspace of vst_instnorm_skip_bwd: vst_instnorm_ws_bytes' layout (slice partials [N][nsplit][C][3]
 // fp64, the {mean g, mean g*xhat} table, the per-image bias sums [N][C] fp64)
 extern "C" size_t vst_instnorm_skip_ws_bytes(int N, int HW, int C) {
-  RedGeom g;
-  if (N <= 0 || HW <= 0 || !red_geom(N, HW, C, g)) return 0;
-  return (size_t)N * g.nsplit * C * 3 * sizeof(double) + (size_t)N * C * (sizeof(float2) + sizeof(double)) + 256;
+  return N <= 0 || HW <= 0 ? 0 : vst_instnorm_ws_bytes(N, HW, C);
 }
 
 // VST_EINVAL for null / non-positive arguments, VST_EUNSUPPORTED for a geometry outside the contract
@@ -1145,43 +1098,27 @@ extern "C" int vst_instnorm_skip_bwd(const float* g_d, const float* g_cat, int C
   if (const int rc = skip_args("instnorm_skip_bwd", g_cat && y && dy && (ws || (!stats && !db)), N, HW, C, Cs, c0, g))
     return rc;
   hipStream_t s = (hipStream_t)stream;
-  double* part = reinterpret_cast<double*>(ws);
-  float2* coef = reinterpret_cast<float2*>(reinterpret_cast<char*>(ws) + (size_t)N * g.nsplit * C * 3 * sizeof(double));
-  double* dbn = reinterpret_cast<double*>(reinterpret_cast<char*>(coef) + (size_t)N * C * sizeof(float2));
-  const bool narrow = fin_cpb(C, N, g.nsplit) == 4;
-  const dim3 fgrid(ceil_div(C, narrow ? 4 : 16), N);
+  const BwdWs w(ws, N, g.nsplit, C, 3, 1, 1);  // tab = the {mean g, mean g*xhat} table, sums = dbn
   if (stats) {
-    hipLaunchKernelGGL(skip_partial_k<true>, dim3(g.nsplit, N), dim3(NRED), 0, s, g_d, g_cat, y, stats, part, HW, C,
+    hipLaunchKernelGGL(skip_partial_k<true>, dim3(g.nsplit, N), dim3(NRED), 0, s, g_d, g_cat, y, stats, w.part, HW, C,
                        Cs, c0, g.LP, g.PG, g.SP, g.nsplit, slope);
-    if (narrow)
-      hipLaunchKernelGGL(in_bwd_finalize_k<4>, fgrid, dim3(256), 0, s, part, stats, coef, dbn, N, HW, C, g.nsplit);
-    else
-      hipLaunchKernelGGL(in_bwd_finalize_k<16>, fgrid, dim3(256), 0, s, part, stats, coef, dbn, N, HW, C, g.nsplit);
+    launch_fin(in_bwd_finalize_k<4>, in_bwd_finalize_k<16>, C, N, g.nsplit, s, w.part, stats, w.tab, w.sums, N, HW, C,
+               g.nsplit);
   } else if (db) {
-    hipLaunchKernelGGL(skip_partial_k<false>, dim3(g.nsplit, N), dim3(NRED), 0, s, g_d, g_cat, y, stats, part, HW, C,
+    hipLaunchKernelGGL(skip_partial_k<false>, dim3(g.nsplit, N), dim3(NRED), 0, s, g_d, g_cat, y, stats, w.part, HW, C,
                        Cs, c0, g.LP, g.PG, g.SP, g.nsplit, slope);
-    if (narrow)
-      hipLaunchKernelGGL(skip_db_finalize_k<4>, fgrid, dim3(256), 0, s, part, dbn, C, g.nsplit);
-    else
-      hipLaunchKernelGGL(skip_db_finalize_k<16>, fgrid, dim3(256), 0, s, part, dbn, C, g.nsplit);
+    launch_fin(skip_db_finalize_k<4>, skip_db_finalize_k<16>, C, N, g.nsplit, s, w.part, w.sums, C, g.nsplit);
   }
   const long total4 = (long)N * HW * C / 4;
   const int blocks = std::max(ceil_div(total4, 256), ceil_div(C, 256));
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(g_d), g_cat,
-                       reinterpret_cast<const float4*>(y), stats, coef, reinterpret_cast<float4*>(dy), total4, HW,
-                       C / 4, Cs, c0, slope, dbn, db, N, accumulate_db);
+                       reinterpret_cast<const float4*>(y), stats, w.tab, reinterpret_cast<float4*>(dy), total4, HW,
+                       C / 4, Cs, c0, slope, w.sums, db, N, accumulate_db);
   };
   if (stats) g_d ? launch(skip_bwd_apply_k<true, true>) : launch(skip_bwd_apply_k<true, false>);
   else g_d ? launch(skip_bwd_apply_k<false, true>) : launch(skip_bwd_apply_k<false, false>);
   return check_launch("instnorm_skip_bwd");
-}
-
-extern "C" size_t vst_instnorm_ws_bytes(int N, int HW, int C) {
-  RedGeom g;
-  if (!red_geom(N, HW, C, g)) return 0;
-  return (size_t)N * g.nsplit * C * 3 * sizeof(double) + (size_t)N * C * (sizeof(float2) + sizeof(double)) +
-         256;
 }
 
 extern "C" int vst_instnorm_stats(const float* x, float* stats, float* ws, int N, int HW, int C,
@@ -1193,23 +1130,14 @@ extern "C" int vst_instnorm_stats(const float* x, float* stats, float* ws, int N
   double* part = reinterpret_cast<double*>(ws);
   hipLaunchKernelGGL(in_partial_k<0>, dim3(g.nsplit, N), dim3(NRED), 0, s, x, (const float*)nullptr,
                      (const float*)nullptr, part, HW, C, g.LP, g.PG, g.SP, g.nsplit, 0, 0.f);
-  if (fin_cpb(C, N, g.nsplit) == 4)
-    hipLaunchKernelGGL(in_finalize_k<4>, dim3(ceil_div(C, 4), N), dim3(256), 0, s, part, stats, N, HW, C, g.nsplit, eps);
-  else
-    hipLaunchKernelGGL(in_finalize_k<16>, dim3(ceil_div(C, 16), N), dim3(256), 0, s, part, stats, N, HW, C, g.nsplit,
-                       eps);
+  launch_fin(in_finalize_k<4>, in_finalize_k<16>, C, N, g.nsplit, s, part, stats, N, HW, C, g.nsplit, eps);
   return check_launch("instnorm_stats");
 }
 
 extern "C" int vst_instnorm_finalize(const double* part, float* stats, int N, int HW, int C, int nsplit,
                                      float eps, void* stream) {
   VST_REQUIRE(part && stats && N > 0 && HW > 0 && C > 0 && nsplit > 0, "instnorm_finalize: bad args");
-  if (fin_cpb(C, N, nsplit) == 4)
-    hipLaunchKernelGGL(in_finalize_k<4>, dim3(ceil_div(C, 4), N), dim3(256), 0, (hipStream_t)stream, part, stats, N,
-                       HW, C, nsplit, eps);
-  else
-    hipLaunchKernelGGL(in_finalize_k<16>, dim3(ceil_div(C, 16), N), dim3(256), 0, (hipStream_t)stream, part, stats,
-                       N, HW, C, nsplit, eps);
+  launch_fin(in_finalize_k<4>, in_finalize_k<16>, C, N, nsplit, (hipStream_t)stream, part, stats, N, HW, C, nsplit, eps);
   return check_launch("instnorm_finalize");
 }
 
@@ -1223,10 +1151,6 @@ extern "C" int vst_instnorm_act_fwd(const float* x, const float* stats, const fl
                      reinterpret_cast<float4*>(y), total4, HW, C / 4, act, slope);
   return check_launch("instnorm_act_fwd");
 }
-
-extern "C" int vst_instnorm_act_bwd_planes(const float* gy, const float* x, const float* stats, float* dx,
-                                           float* db, float* ws, int N, int HW, int C, int act, float slope,
-                                           int accumulate_db, void* planes, long ldp, void* stream);
 
 extern "C" int vst_instnorm_act_fwd_cp(const float* x, const float* stats, const float* residual, float* y,
                                        float* xt, int N, int H, int W, int C, int act, float slope, int pad,
@@ -1254,17 +1178,29 @@ extern "C" int vst_instnorm_act_fwd_planes(const float* x, const float* stats, c
   return check_launch("instnorm_act_fwd_planes");
 }
 
-extern "C" int vst_instnorm_act_bwd(const float* gy, const float* x, const float* stats, float* dx,
-                                    float* db, float* ws, int N, int HW, int C, int act, float slope,
-                                    int accumulate_db, void* stream) {
-  return vst_instnorm_act_bwd_planes(gy, x, stats, dx, db, ws, N, HW, C, act, slope, accumulate_db, nullptr,
-                                     0, stream);
-}
-
 // IN backward after its partials are in ws: finalize, bias gradient, apply (+ planes).
 static int in_bwd_tail(const float* gy, const float* x, const float* stats, float* dx, float* db, float* ws,
                        int N, int HW, int C, int act, float slope, int accumulate_db, void* planes, long ldp,
-                       const RedGeom& g, hipStream_t s, void* apl = nullptr);
+                       const RedGeom& g, hipStream_t s, void* apl = nullptr) {
+  const BwdWs w(ws, N, g.nsplit, C, 3, 1, 1);  // tab = the {mean g, mean g*xhat} table, sums = dbn
+  launch_fin(in_bwd_finalize_k<4>, in_bwd_finalize_k<16>, C, N, g.nsplit, s, w.part, stats, w.tab, w.sums, N, HW, C,
+             g.nsplit);
+  // the bias gradient (sum over n of dbn) is taken by the apply pass's first blocks
+  if (planes) {
+    const long P = (long)N * HW;
+    hipLaunchKernelGGL(in_bwd_apply_planes_k, dim3(ceil_div(P, 64), ceil_div(C, 64)), dim3(256), 0, s, gy, x, stats,
+                       w.tab, dx, reinterpret_cast<__bf16*>(planes), P, HW, C, ldp, act, slope, w.sums, db, N,
+                       accumulate_db, reinterpret_cast<__bf16*>(apl));
+    return check_launch("instnorm_act_bwd_planes");
+  }
+  const long total4 = (long)N * HW * C / 4;
+  VST_REQUIRE(!db || total4 >= C, "instnorm_act_bwd: fewer elements than channels");
+  hipLaunchKernelGGL(in_bwd_apply_k, dim3(ceil_div(total4, 256)), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(x), stats,
+                     w.tab, reinterpret_cast<float4*>(dx), total4, HW, C / 4, act, slope, w.sums, db, N,
+                     accumulate_db, reinterpret_cast<__bf16*>(apl));
+  return check_launch("instnorm_act_bwd");
+}
 
 extern "C" int vst_instnorm_act_bwd_planes(const float* gy, const float* x, const float* stats, float* dx,
                                            float* db, float* ws, int N, int HW, int C, int act, float slope,
@@ -1277,6 +1213,13 @@ extern "C" int vst_instnorm_act_bwd_planes(const float* gy, const float* x, cons
   hipLaunchKernelGGL(in_partial_k<1>, dim3(g.nsplit, N), dim3(NRED), 0, s, x, gy, stats, part, HW, C,
                      g.LP, g.PG, g.SP, g.nsplit, act, slope);
   return in_bwd_tail(gy, x, stats, dx, db, ws, N, HW, C, act, slope, accumulate_db, planes, ldp, g, s);
+}
+
+extern "C" int vst_instnorm_act_bwd(const float* gy, const float* x, const float* stats, float* dx,
+                                    float* db, float* ws, int N, int HW, int C, int act, float slope,
+                                    int accumulate_db, void* stream) {
+  return vst_instnorm_act_bwd_planes(gy, x, stats, dx, db, ws, N, HW, C, act, slope, accumulate_db, nullptr,
+                                     0, stream);
 }
 
 // vst_instnorm_act_bwd_planes that writes dx ONLY as its NHWC bf16 planes apl [3][N*HW*C] (the A operand of the x6
@@ -1301,9 +1244,7 @@ extern "C" int vst_instnorm_act_bwd_planes_apre(const float* gy, const float* x,
 // and a launch) is needed; then the finalize / apply (+ dy planes).  Workspace: the
 // IN partials [N][ns][C][3] + coefficients, then the data gradient's.  x6 arithmetic, H W % 32 == 0.
 static size_t in_epi_ws_bytes_al(int N, int H, int W, int C) {
-  const size_t ns = bf_dgrad_refl1_inb_slices(H, W);
-  return ((size_t)N * ns * C * 3 * sizeof(double) + (size_t)N * C * (sizeof(float2) + sizeof(double)) + 256 + 255) /
-         256 * 256;
+  return (BwdWs(nullptr, N, bf_dgrad_refl1_inb_slices(H, W), C, 3, 1, 1).bytes + 255) / 256 * 256;
 }
 
 extern "C" size_t vst_conv2d_dgrad_refl_in_epi_ws_bytes(int N, int H, int W, int Cy, int Cx, int math) {
@@ -1351,36 +1292,6 @@ extern "C" int vst_conv2d_dgrad_refl_in_epi(const float* dy, const void* wsplit,
                                        nullptr, stream);
 }
 
-static int in_bwd_tail(const float* gy, const float* x, const float* stats, float* dx, float* db, float* ws,
-                       int N, int HW, int C, int act, float slope, int accumulate_db, void* planes, long ldp,
-                       const RedGeom& g, hipStream_t s, void* apl) {
-  double* part = reinterpret_cast<double*>(ws);
-  float2* coef = reinterpret_cast<float2*>(reinterpret_cast<char*>(ws) +
-                                           (size_t)N * g.nsplit * C * 3 * sizeof(double));
-  double* dbn = reinterpret_cast<double*>(reinterpret_cast<char*>(coef) + (size_t)N * C * sizeof(float2));
-  if (fin_cpb(C, N, g.nsplit) == 4)
-    hipLaunchKernelGGL(in_bwd_finalize_k<4>, dim3(ceil_div(C, 4), N), dim3(256), 0, s, part, stats, coef, dbn,
-                     N, HW, C, g.nsplit);
-  else
-    hipLaunchKernelGGL(in_bwd_finalize_k<16>, dim3(ceil_div(C, 16), N), dim3(256), 0, s, part, stats, coef, dbn,
-                     N, HW, C, g.nsplit);
-  // the bias gradient (sum over n of dbn) is taken by the apply pass's first blocks
-  if (planes) {
-    const long P = (long)N * HW;
-    hipLaunchKernelGGL(in_bwd_apply_planes_k, dim3(ceil_div(P, 64), ceil_div(C, 64)), dim3(256), 0, s, gy, x, stats,
-                       coef, dx, reinterpret_cast<__bf16*>(planes), P, HW, C, ldp, act, slope, dbn, db, N,
-                       accumulate_db, reinterpret_cast<__bf16*>(apl));
-    return check_launch("instnorm_act_bwd_planes");
-  }
-  const long total4 = (long)N * HW * C / 4;
-  VST_REQUIRE(!db || total4 >= C, "instnorm_act_bwd: fewer elements than channels");
-  hipLaunchKernelGGL(in_bwd_apply_k, dim3(ceil_div(total4, 256)), dim3(256), 0, s,
-                     reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(x), stats,
-                     coef, reinterpret_cast<float4*>(dx), total4, HW, C / 4, act, slope, dbn, db, N,
-                     accumulate_db, reinterpret_cast<__bf16*>(apl));
-  return check_launch("instnorm_act_bwd");
-}
-
 extern "C" int vst_act_bwd(const float* gy, const float* y, float* dx, long n, int act, float slope,
                            void* stream) {
   VST_REQUIRE(gy && y && dx, "act_bwd: null pointer");
@@ -1415,8 +1326,7 @@ extern "C" int vst_channel_sum(const float* x, float* db, float* ws, long NHW, i
 extern "C" size_t vst_instnorm_affine_ws_bytes(int N, int HW, int C) {
   RedGeom g;
   if (!red_geom(N, HW, C, g)) return 0;
-  return (size_t)N * g.nsplit * C * 4 * sizeof(double) + (size_t)N * C * (sizeof(float2) + 4 * sizeof(double)) +
-         256;
+  return BwdWs(nullptr, N, g.nsplit, C, 4, 1, 4).bytes;
 }
 
 extern "C" int vst_instnorm_affine_fwd(const float* x, const float* stats, const float* gamma,
@@ -1442,20 +1352,17 @@ extern "C" int vst_instnorm_affine_bwd(const float* gy, const float* x, const fl
   VST_REQUIRE(gy && x && stats && gamma && beta && dx && ws && red_geom(N, HW, C, g),
               "instnorm_affine_bwd: bad args (C must be a multiple of 4, at most 1024)");
   hipStream_t s = (hipStream_t)stream;
-  double* part = reinterpret_cast<double*>(ws);
-  char* p = reinterpret_cast<char*>(ws) + (size_t)N * g.nsplit * C * 4 * sizeof(double);
-  float2* coef = reinterpret_cast<float2*>(p);
-  double* sums = reinterpret_cast<double*>(p + (size_t)N * C * sizeof(float2));
+  const BwdWs w(ws, N, g.nsplit, C, 4, 1, 4);
   hipLaunchKernelGGL(in_aff_partial_k, dim3(g.nsplit, N), dim3(NRED), 0, s, x, gy, stats, gamma, beta,
-                     gate, gate_mult, part, HW, C, g.LP, g.PG, g.SP, g.nsplit, act, slope);
-  hipLaunchKernelGGL(in_aff_finalize_k, dim3(ceil_div(C, 64), N), dim3(256), 0, s, part, stats, gamma,
-                     coef, sums, N, HW, C, g.nsplit);
-  hipLaunchKernelGGL(in_aff_param_grad_k, dim3(1), dim3(256), 0, s, sums, dgamma, dbeta, dbias, gate,
+                     gate, gate_mult, w.part, HW, C, g.LP, g.PG, g.SP, g.nsplit, act, slope);
+  hipLaunchKernelGGL(in_aff_finalize_k, dim3(ceil_div(C, 64), N), dim3(256), 0, s, w.part, stats, gamma,
+                     w.tab, w.sums, N, HW, C, g.nsplit);
+  hipLaunchKernelGGL(in_aff_param_grad_k, dim3(1), dim3(256), 0, s, w.sums, dgamma, dbeta, dbias, gate,
                      gate_mult, dgate, N, C, accumulate);
   const long total4 = (long)N * HW * C / 4;
   hipLaunchKernelGGL(in_aff_bwd_apply_k, dim3(ceil_div(total4, 256)), dim3(256), 0, s,
                      reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(x), stats, gamma,
-                     beta, gate, gate_mult, coef, reinterpret_cast<float4*>(dx), total4, HW, C / 4, act,
+                     beta, gate, gate_mult, w.tab, reinterpret_cast<float4*>(dx), total4, HW, C / 4, act,
                      slope);
   return check_launch("instnorm_affine_bwd");
 }
@@ -1465,8 +1372,7 @@ extern "C" int vst_instnorm_affine_bwd(const float* gy, const float* x, const fl
 extern "C" size_t vst_cond_instnorm_ws_bytes(int N, int HW, int C) {
   RedGeom g;
   if (N <= 0 || HW <= 0 || !red_geom(N, HW, C, g)) return 0;
-  return (size_t)N * g.nsplit * C * 3 * sizeof(double) + (size_t)N * C * (2 * sizeof(float2) + 3 * sizeof(double)) +
-         256;
+  return BwdWs(nullptr, N, g.nsplit, C, 3, 2, 3).bytes;
 }
 
 static bool cond_args_ok(int N, int HW, int C, int Cl, int S, int act, RedGeom& g) {
@@ -1499,17 +1405,14 @@ extern "C" int vst_cond_instnorm_bwd(const float* gy, const float* x, const floa
                   cond_args_ok(N, HW, C, Cl, S, act, g),
               "cond_instnorm_bwd: bad args (C a multiple of 4, at most 1024; 0 < Cl <= C; S >= 1; act none | relu)");
   hipStream_t s = (hipStream_t)stream;
-  double* part = reinterpret_cast<double*>(ws);
-  char* p = reinterpret_cast<char*>(ws) + (size_t)N * g.nsplit * C * 3 * sizeof(double);
-  float2* tab = reinterpret_cast<float2*>(p);
-  float2* coef = tab + (size_t)N * C;
-  double* sums = reinterpret_cast<double*>(coef + (size_t)N * C);
+  const BwdWs w(ws, N, g.nsplit, C, 3, 2, 3);
+  float2 *tab = w.tab, *coef = w.tab + (size_t)N * C;
   hipLaunchKernelGGL(cond_partial_k, dim3(g.nsplit, N), dim3(NRED), 0, s, x, gy, stats, sid, embed, bn_weight,
-                     bn_bias, part, HW, C, Cl, S, g.LP, g.PG, g.SP, g.nsplit, act);
-  hipLaunchKernelGGL(cond_finalize_k, dim3(ceil_div(C, 64), N), dim3(256), 0, s, part, stats, sid, embed,
-                     bn_weight, bn_bias, tab, coef, sums, N, HW, C, Cl, S, g.nsplit);
+                     bn_bias, w.part, HW, C, Cl, S, g.LP, g.PG, g.SP, g.nsplit, act);
+  hipLaunchKernelGGL(cond_finalize_k, dim3(ceil_div(C, 64), N), dim3(256), 0, s, w.part, stats, sid, embed,
+                     bn_weight, bn_bias, tab, coef, w.sums, N, HW, C, Cl, S, g.nsplit);
   if (dembed || dbn_weight || dbn_bias || dbias)
-    hipLaunchKernelGGL(cond_param_grad_k, dim3(1), dim3(256), 0, s, sums, sid, embed, bn_weight, bn_bias, dembed,
+    hipLaunchKernelGGL(cond_param_grad_k, dim3(1), dim3(256), 0, s, w.sums, sid, embed, bn_weight, bn_bias, dembed,
                        dbn_weight, dbn_bias, dbias, N, C, Cl, S, accumulate);
   const long total4 = (long)N * HW * C / 4;
   hipLaunchKernelGGL(cond_bwd_apply_k, dim3(ceil_div(total4, 256)), dim3(256), 0, s,

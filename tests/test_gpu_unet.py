@@ -29,14 +29,17 @@ DEV = "cuda"
 F64 = torch.float64
 SLOPE = R.f32(0.2)
 INST = functools.partial(nn.InstanceNorm2d, affine=False, track_running_stats=False)
-GEOMS = {k: R.IN_CASE[k][1] for k in ("tiny_hw", "c4", "c8", "tail_cpb4", "fold4_unrolled", "lp18")}
+GEOMS = {k: R.IN_CASE[k][1] for k in ("tiny_hw", "c4", "c8", "tail_cpb4", "fold4_unrolled", "lp18", "part_unrolled_6")}
 GEOMS["map_1x2"] = (2, 1, 2, 32)
 # Input scale per geometry: y = 2 N(0, 1) + 0.5, except on the 2-pixel map.  There x_hat = +-a with
 # a^2 = h^2 / (h^2 + eps) (h: half the difference of the two values), and the InstanceNorm backward is
 # dy = rstd (g - mean g) (1 - a^2): at h ~ 2 the two terms cancel to eps / h^2 = 2.5e-6 of their size, so the fp32
 # rounding of the stored mean and rstd (2^-24 relative) alone is 2e-2 of the result, in any fp32 implementation.
 # At h ~ sqrt(eps) = 3e-3 (y = 3e-3 N(0, 1)) 1 - a^2 ~ 0.5 and the problem is as well conditioned as the others.
-Y_SCALE = {"map_1x2": (3e-3, 0.0)}
+# part_unrolled_6 (rows reach the 4x unrolled loop of the partial walk, with a remainder and a ragged last slice)
+# has 2.8 M elements, and no seed keeps that many Gaussian values clear of 0; the signs are intrinsic to these
+# kernels, so its values are moved away from 0 by a gap instead: y = sign(r) (2 |r| + 0.2), r = N(0, 1).
+Y_SCALE = {"map_1x2": (3e-3, 0.0), "part_unrolled_6": (2.0, 0.0, 0.2)}
 SENTINEL = -12345.678
 
 
@@ -68,8 +71,11 @@ def _op_data(geom, use_stats):
     base = 4000 + 50 * sorted(GEOMS).index(geom)
     for seed in range(base, base + 50):
         gen = torch.Generator().manual_seed(seed)
-        scale, shift = Y_SCALE.get(geom, (2.0, 0.5))
-        y = scale * torch.randn(N, H, W, C, generator=gen) + shift
+        scale, shift, gap = (Y_SCALE.get(geom, (2.0, 0.5)) + (0.0,))[:3]
+        r = torch.randn(N, H, W, C, generator=gen)
+        y = scale * r + shift
+        if gap:
+            y = y + gap * torch.sign(r)
         z = U.skip_fwd(R.nchw64(y), use_stats, SLOPE)[2]
         if float(z.abs().min() / z.abs().max()) >= 1e-6:
             break
