@@ -131,6 +131,14 @@ SIGNATURES = {
     "vst_cond_instnorm_ws_bytes": (SZ, [I, I, I]),
     "vst_cond_instnorm_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "vst_cond_instnorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "vst_adain_ws_bytes": (SZ, [I, I, I]),
+    "vst_adain_fwd": (I, [P, P, P, P, P, I, I, I, I, F, P]),
+    "vst_adain_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, F, I, P]),
+    "vst_act_fwd": (I, [P, P, L, I, F, P]),
+    "vst_avgpool2_fwd": (I, [P, P, I, I, I, I, P]),
+    "vst_avgpool2_bwd": (I, [P, P, I, I, I, I, P]),
+    "vst_merge_fwd": (I, [P, P, P, I, I, I, I, I, F, P]),
+    "vst_merge_bwd": (I, [P, P, P, I, I, I, I, I, F, P]),
     "vst_instnorm_skip_ws_bytes": (SZ, [I, I, I]),
     "vst_instnorm_skip_fwd": (I, [P, P, P, P, I, I, I, I, I, F, P]),
     "vst_instnorm_skip_bwd": (I, [P, P, I, I, P, P, P, P, I, P, I, I, I, F, P]),

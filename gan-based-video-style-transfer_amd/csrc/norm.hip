@@ -10,8 +10,8 @@
 // launches ~512 blocks (64x64x256 res tensors and 256x256x64 outer tensors alike).
 //
 // That walk is written once (slice_partials): every family's partial kernel (plain, affine,
-// conditional, U-Net skip) hands it how a pixel row is loaded and what a pixel adds to the sums.
-// Affine and conditional IN are one operator, z = x * al + sh with per-(n, c) coefficients, and share
+// conditional, adaptive, U-Net skip) hands it how a pixel row is loaded and what a pixel adds to the sums.
+// Affine, conditional and adaptive IN are one operator, z = x * al + sh with per-(n, c) coefficients, and share
 // the mod_* bodies; they differ in the coefficient provider ({al, sh} for (n, c)) and in their
 // parameter-gradient kernels.
 #include "common.h"
@@ -870,6 +870,77 @@ __global__ void cond_bwd_apply_k(const float4* __restrict__ gy, const float4* __
                 1.f, reinterpret_cast<const float2*>(coef), dx, total4, HW, C4, act, 0.f);
 }
 
+// ---- adaptive InstanceNorm (AdaIN, StarGAN v2 core/model.py:67-77) ------------------------------
+// y = act((1 + gamma[n, c]) * xhat + beta[n, c]) with {gamma, beta} = the halves of the style projection
+// h[n] = fc(s[n]) ([N][2C]): A = 1 + gamma, B = beta, so al = (1 + gamma) * rstd, sh = beta - mean * al.  The
+// coefficients are tabulated once per pass (every sample has its own row, nothing is shared over n); the
+// parameter gradient is dh itself, dgamma[n, c] = sum_p gz * xhat and dbeta[n, c] = sum_p gz.
+// tab[n*C + c] = {al, sh}, one thread per (n, c)
+__global__ void adain_coef_k(const float* __restrict__ stats, const float* __restrict__ h, float2* __restrict__ tab,
+                             int N, int C) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * C) return;
+  const int n = i / C, c = i % C;
+  const float mean = stats[2 * (long)i], rstd = stats[2 * (long)i + 1];
+  const float al = (1.f + h[(long)n * 2 * C + c]) * rstd;
+  tab[i] = make_float2(al, h[(long)n * 2 * C + C + c] - mean * al);
+}
+
+__global__ void adain_apply_k(const float4* __restrict__ x, const float4* __restrict__ tab, float4* __restrict__ y,
+                              long total4, int HW, int C4, int act, float slope) {
+  mod_apply(x, TabCoef{reinterpret_cast<const float2*>(tab), 4 * C4}, nullptr, 0.f, nullptr, y, total4, HW, C4, act,
+            slope);
+}
+
+__global__ __launch_bounds__(NRED) void adain_partial_k(const float* __restrict__ x, const float* __restrict__ gy,
+                                                        const float* __restrict__ stats,
+                                                        const float2* __restrict__ tab, double* __restrict__ part,
+                                                        int HW, int C, int LP, int PG, int SP, int nsplit, int act,
+                                                        float slope) {
+  mod_partial<3>(x, gy, stats, TabCoef{tab, C}, 1.f, part, HW, C, LP, PG, SP, nsplit, act, slope);
+}
+
+// coef[n*C+c] = {mean gz, mean gz*xhat} for the backward apply; sums[n*C+c] = {sum gz, sum gz*xhat, dbias term}
+__global__ void adain_finalize_k(const double* __restrict__ part, const float2* __restrict__ tab,
+                                 float2* __restrict__ coef, double* __restrict__ sums, int N, int HW, int C,
+                                 int nsplit) {
+  double a[3];
+  const int n = blockIdx.y;
+  if (!fold_slices<3>(part, n, C, nsplit, a)) return;
+  const int idx = n * C + blockIdx.x * 64 + (threadIdx.x & 63);
+  sums[3 * idx + 0] = a[0];
+  sums[3 * idx + 1] = a[1];
+  sums[3 * idx + 2] = (double)tab[idx].x * bwd_coef(a, HW, coef[idx]);
+}
+
+// a thread per (n, c): dh[n][c] = sum gz*xhat, dh[n][C + c] = sum gz; the first C threads also take the conv
+// bias gradient (sum over n, fixed order)
+__global__ void adain_param_grad_k(const double* __restrict__ sums, float* __restrict__ dh,
+                                   float* __restrict__ dbias, int N, int C, int accumulate) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * C) return;
+  if (dh) {
+    const int n = i / C, c = i % C;
+    float* row = dh + (long)n * 2 * C;
+    const float dg = (float)sums[3 * (long)i + 1], db = (float)sums[3 * (long)i];
+    row[c] = accumulate ? row[c] + dg : dg;
+    row[C + c] = accumulate ? row[C + c] + db : db;
+  }
+  if (dbias && i < C) {
+    double s = 0.0;
+    for (int n = 0; n < N; ++n) s += sums[3 * ((long)n * C + i) + 2];
+    dbias[i] = accumulate ? dbias[i] + (float)s : (float)s;
+  }
+}
+
+__global__ void adain_bwd_apply_k(const float4* __restrict__ gy, const float4* __restrict__ x,
+                                  const float4* __restrict__ stats, const float4* __restrict__ tab,
+                                  const float4* __restrict__ coef, float4* __restrict__ dx, long total4, int HW,
+                                  int C4, int act, float slope) {
+  mod_bwd_apply(gy, x, reinterpret_cast<const float*>(stats), TabCoef{reinterpret_cast<const float2*>(tab), 4 * C4},
+                1.f, reinterpret_cast<const float2*>(coef), dx, total4, HW, C4, act, slope);
+}
+
 // ---- running statistics (nn.InstanceNorm2d(track_running_stats=True), StarGAN model.py:13-16) ---
 // ATen instance_norm: batch_norm over (1, N*C, HW) with the running buffers repeated N times, then
 // the N copies averaged: rm = (1-m) rm + m * mean_n(mean_nc); rv = (1-m) rv + m * mean_n(var_nc *
@@ -1420,6 +1491,59 @@ extern "C" int vst_cond_instnorm_bwd(const float* gy, const float* x, const floa
                      reinterpret_cast<const float4*>(stats), reinterpret_cast<const float4*>(tab),
                      reinterpret_cast<const float4*>(coef), reinterpret_cast<float4*>(dx), total4, HW, C / 4, act);
   return check_launch("cond_instnorm_bwd");
+}
+
+// workspace: vst_cond_instnorm_ws_bytes' layout (slice partials [N][nsplit][C][3] fp64, the {al, sh} and
+// {mean gz, mean gz*xhat} tables, the folded sums [N][C][3] fp64).  The forward uses the first N*C float2 only.
+extern "C" size_t vst_adain_ws_bytes(int N, int HW, int C) {
+  RedGeom g;
+  if (N <= 0 || HW <= 0 || !red_geom(N, HW, C, g)) return 0;
+  return BwdWs(nullptr, N, g.nsplit, C, 3, 2, 3).bytes;
+}
+
+static bool adain_args_ok(int N, int HW, int C, int act, RedGeom& g) {
+  return N > 0 && HW > 0 && C > 0 && red_geom(N, HW, C, g) && (act == VST_ACT_NONE || act == VST_ACT_LRELU);
+}
+
+extern "C" int vst_adain_fwd(const float* x, const float* stats, const float* h, float* y, float* ws, int N, int HW,
+                             int C, int act, float slope, void* stream) {
+  RedGeom g;
+  VST_REQUIRE(x && stats && h && y && ws && adain_args_ok(N, HW, C, act, g),
+              "adain_fwd: bad args (C a multiple of 4, at most 1024; act none | lrelu)");
+  hipStream_t s = (hipStream_t)stream;
+  float2* tab = reinterpret_cast<float2*>(ws);
+  hipLaunchKernelGGL(adain_coef_k, dim3(ceil_div((long)N * C, 256)), dim3(256), 0, s, stats, h, tab, N, C);
+  const long total4 = (long)N * HW * C / 4;
+  hipLaunchKernelGGL(adain_apply_k, dim3(ceil_div(total4, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(x),
+                     reinterpret_cast<const float4*>(tab), reinterpret_cast<float4*>(y), total4, HW, C / 4, act,
+                     slope);
+  return check_launch("adain_fwd");
+}
+
+extern "C" int vst_adain_bwd(const float* gy, const float* x, const float* stats, const float* h, float* dx,
+                             float* dh, float* dbias, float* ws, int N, int HW, int C, int act, float slope,
+                             int accumulate, void* stream) {
+  RedGeom g;
+  VST_REQUIRE(gy && x && stats && h && dx && ws && adain_args_ok(N, HW, C, act, g),
+              "adain_bwd: bad args (C a multiple of 4, at most 1024; act none | lrelu)");
+  hipStream_t s = (hipStream_t)stream;
+  const BwdWs w(ws, N, g.nsplit, C, 3, 2, 3);
+  float2 *tab = w.tab, *coef = w.tab + (size_t)N * C;
+  hipLaunchKernelGGL(adain_coef_k, dim3(ceil_div((long)N * C, 256)), dim3(256), 0, s, stats, h, tab, N, C);
+  hipLaunchKernelGGL(adain_partial_k, dim3(g.nsplit, N), dim3(NRED), 0, s, x, gy, stats, tab, w.part, HW, C, g.LP,
+                     g.PG, g.SP, g.nsplit, act, slope);
+  hipLaunchKernelGGL(adain_finalize_k, dim3(ceil_div(C, 64), N), dim3(256), 0, s, w.part, tab, coef, w.sums, N, HW, C,
+                     g.nsplit);
+  if (dh || dbias)
+    hipLaunchKernelGGL(adain_param_grad_k, dim3(ceil_div((long)N * C, 256)), dim3(256), 0, s, w.sums, dh, dbias, N, C,
+                       accumulate);
+  const long total4 = (long)N * HW * C / 4;
+  hipLaunchKernelGGL(adain_bwd_apply_k, dim3(ceil_div(total4, 256)), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(x),
+                     reinterpret_cast<const float4*>(stats), reinterpret_cast<const float4*>(tab),
+                     reinterpret_cast<const float4*>(coef), reinterpret_cast<float4*>(dx), total4, HW, C / 4, act,
+                     slope);
+  return check_launch("adain_bwd");
 }
 
 extern "C" int vst_instnorm_running_update(const float* stats, float* running_mean, float* running_var,

@@ -16,6 +16,10 @@ library's NHWC layout on the device.  Backward passes are themselves ``vst::`` o
         ConditionalBatchNorm2d (+ ReLU); sid a device int32 [N], the embedding rows gathered by the kernel
   vst::instance_norm_skip(y, normalize, slope) GAN-based networks.py:468-535, the U-Net skip connection under its
         in-place activations: (lrelu(z), relu(z)), z = InstanceNorm2d(affine=False)(y) or y (normalize=False)
+  vst::adain_act(x, h, act, slope)             StarGANv2AdvCon core/model.py:67-77 AdaIN (+ LeakyReLU); h = fc(s) [N, 2C]
+        (the fc itself, like every nn.Linear of these nets, is vst::conv2d over [B, K, 1, 1])
+  vst::avg_pool2(x)                            F.avg_pool2d(x, 2), core/model.py:45-55
+  vst::merge(a, b, mode, scale)                core/model.py:62-64, :116-120: (a + f(b)) * scale, f = identity | pool | up
   vst::warp_bilinear(x, flow)                  utils/flowtools.py:18-32 (F.grid_sample, zeros)
   vst::fbcheck(flow_fw, flow_bw)               utils/flowtools.py:34-58 (fbcCheckTorch)
   vst::temporal_loss(a, b, flow, mask, lam)    CycleGANCon cycle_gan_model.py:191-204
@@ -360,6 +364,146 @@ def _ins_bwd(ctx, g_d, g_skip):
 instance_norm_skip.register_autograd(_ins_bwd, setup_context=_ins_setup)
 
 
+# ---------------------------------------------------------------------------------- adain_act
+def _adain_args(x, h, act):
+    if act not in ("none", "lrelu"):
+        raise ValueError("vst::adain_act: act must be 'none' or 'lrelu'")
+    ops._dev_check(x, h)
+    if h.dim() != 2 or h.shape[0] != x.shape[0] or h.shape[1] != 2 * x.shape[1] or x.shape[1] % 4:
+        raise ValueError("vst::adain_act: h [N, 2*C] for x [N, C, H, W] with C %% 4 == 0, got %s and %s"
+                         % (tuple(h.shape), tuple(x.shape)))
+    y = _nhwc(x)
+    return y, ops.instnorm_stats(y), h.detach().contiguous()
+
+
+@torch.library.custom_op("vst::adain_act", mutates_args=())
+def adain_act(x: Tensor, h: Tensor, act: str, slope: float) -> Tensor:
+    """StarGAN v2 core/model.py:67-77 AdaIN (+ LeakyReLU): act((1 + gamma) * InstanceNorm2d(x) + beta) with
+    {gamma, beta} = h.chunk(2, 1), h [N, 2*C] the style projection fc(s).  act in none | lrelu."""
+    y, st, hh = _adain_args(x, h, act)
+    return ops.nhwc_to_nchw(ops.adain_fwd(y, st, hh, act, slope), x.shape[1])
+
+
+@adain_act.register_fake
+def _(x, h, act, slope):
+    return torch.empty_like(x)
+
+
+@torch.library.custom_op("vst::adain_act_backward", mutates_args=())
+def adain_act_backward(grad: Tensor, x: Tensor, h: Tensor, act: str, slope: float) -> Tuple[Tensor, Tensor]:
+    """(dx, dh) of vst::adain_act."""
+    y, st, hh = _adain_args(x, h, act)
+    dh = torch.empty_like(hh)
+    dx = ops.adain_bwd(_nhwc(grad), y, st, hh, act, slope, dh=dh)
+    return ops.nhwc_to_nchw(dx, x.shape[1]), dh
+
+
+@adain_act_backward.register_fake
+def _(grad, x, h, act, slope):
+    return torch.empty_like(x), torch.empty_like(h)
+
+
+def _adain_setup(ctx, inputs, output):
+    x, h, act, slope = inputs
+    ctx.save_for_backward(x, h)
+    ctx.conf = (act, slope)
+
+
+def _adain_bwd(ctx, grad):
+    x, h = ctx.saved_tensors
+    dx, dh = torch.ops.vst.adain_act_backward(grad.contiguous(), x, h, *ctx.conf)
+    return dx, dh, None, None
+
+
+adain_act.register_autograd(_adain_bwd, setup_context=_adain_setup)
+
+
+# ------------------------------------------------------------------------- avg_pool2 / merge
+def _c4(x, what):
+    ops._dev_check(x)
+    if x.dim() != 4 or x.shape[1] % 4:
+        raise ValueError("vst::%s: [N, C, H, W] with C %% 4 == 0, got %s" % (what, tuple(x.shape)))
+
+
+@torch.library.custom_op("vst::avg_pool2", mutates_args=())
+def avg_pool2(x: Tensor) -> Tensor:
+    """F.avg_pool2d(x, 2) of [N, C, H, W] with even H and W (core/model.py:45-55)."""
+    _c4(x, "avg_pool2")
+    return ops.nhwc_to_nchw(ops.avgpool2(_nhwc(x)), x.shape[1])
+
+
+@avg_pool2.register_fake
+def _(x):
+    return x.new_empty((x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2))
+
+
+@torch.library.custom_op("vst::avg_pool2_backward", mutates_args=())
+def avg_pool2_backward(grad: Tensor) -> Tensor:
+    _c4(grad, "avg_pool2_backward")
+    return ops.nhwc_to_nchw(ops.avgpool2_bwd(_nhwc(grad)), grad.shape[1])
+
+
+@avg_pool2_backward.register_fake
+def _(grad):
+    return grad.new_empty((grad.shape[0], grad.shape[1], 2 * grad.shape[2], 2 * grad.shape[3]))
+
+
+def _ap_bwd(ctx, grad):
+    return torch.ops.vst.avg_pool2_backward(grad.contiguous())
+
+
+avg_pool2.register_autograd(_ap_bwd, setup_context=lambda ctx, inputs, output: None)
+
+
+def _merge_b_nchw(shape, mode):
+    N, C, H, W = shape
+    if mode not in ops.MERGE:
+        raise ValueError("vst::merge: mode must be one of %s" % sorted(ops.MERGE))
+    return {"same": (N, C, H, W), "pool": (N, C, 2 * H, 2 * W), "up": (N, C, H // 2, W // 2)}[mode]
+
+
+@torch.library.custom_op("vst::merge", mutates_args=())
+def merge(a: Tensor, b: Tensor, mode: str, scale: float) -> Tensor:
+    """(a + f(b)) * scale: the residual merge of ResBlk / AdainResBlk (core/model.py:62-64, :116-120) with the
+    shortcut's resampling folded in; mode 'same' (f = identity), 'pool' (f = avg_pool2d(., 2), b at twice a's
+    resolution) or 'up' (f = nearest 2x upsampling, b at half a's resolution)."""
+    _c4(a, "merge")
+    _c4(b, "merge")
+    if tuple(b.shape) != _merge_b_nchw(a.shape, mode):
+        raise ValueError("vst::merge %r: a %s and b %s do not fit" % (mode, tuple(a.shape), tuple(b.shape)))
+    return ops.nhwc_to_nchw(ops.merge(_nhwc(a), _nhwc(b), mode, scale), a.shape[1])
+
+
+@merge.register_fake
+def _(a, b, mode, scale):
+    return torch.empty_like(a)
+
+
+@torch.library.custom_op("vst::merge_backward", mutates_args=())
+def merge_backward(grad: Tensor, mode: str, scale: float) -> Tuple[Tensor, Tensor]:
+    """(da, db) of vst::merge from one pass over grad."""
+    _c4(grad, "merge_backward")
+    ga, gb = ops.merge_bwd(_nhwc(grad), mode, scale)
+    return ops.nhwc_to_nchw(ga, grad.shape[1]), ops.nhwc_to_nchw(gb, grad.shape[1])
+
+
+@merge_backward.register_fake
+def _(grad, mode, scale):
+    return torch.empty_like(grad), grad.new_empty(_merge_b_nchw(grad.shape, mode))
+
+
+def _merge_setup(ctx, inputs, output):
+    ctx.conf = (inputs[2], inputs[3])
+
+
+def _merge_bwd(ctx, grad):
+    ga, gb = torch.ops.vst.merge_backward(grad.contiguous(), *ctx.conf)
+    return ga, gb, None, None
+
+
+merge.register_autograd(_merge_bwd, setup_context=_merge_setup)
+
+
 # ------------------------------------------------------------------------------------ flow
 @torch.library.custom_op("vst::warp_bilinear", mutates_args=())
 def warp_bilinear(x: Tensor, flow: Tensor) -> Tensor:
@@ -653,4 +797,5 @@ OPS: List[str] = ["conv2d", "conv2d_backward", "conv_transpose2d", "conv_transpo
                   "fbcheck", "temporal_loss", "temporal_loss_backward", "temporal_sqdiff", "temporal_sqdiff_backward",
                   "resize_bilinear", "gram", "gram_backward", "adam_", "ruder_stack", "ruder_stack_backward",
                   "ruder_temporal", "ruder_temporal_backward", "cond_instance_norm", "cond_instance_norm_backward",
-                  "instance_norm_skip", "instance_norm_skip_backward"]
+                  "instance_norm_skip", "instance_norm_skip_backward", "adain_act", "adain_act_backward",
+                  "avg_pool2", "avg_pool2_backward", "merge", "merge_backward"]

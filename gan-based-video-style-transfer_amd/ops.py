@@ -1094,6 +1094,111 @@ def cond_instnorm_bwd(g, y, stats, sid, embed, bn_w, bn_b, act="none", dembed=No
     return dx
 
 
+def _adain_check(y, stats, h, act):
+    _dev_check(y, stats, h)
+    if y.dim() != 4 or tuple(stats.shape) != (y.shape[0], y.shape[-1], 2) or \
+            tuple(h.shape) != (y.shape[0], 2 * y.shape[-1]):
+        raise ValueError("adain: y NHWC [N, H, W, C] with stats [N, C, 2] and h [N, 2*C], got %s, %s, %s" %
+                         (tuple(y.shape), tuple(stats.shape), tuple(h.shape)))
+    if act not in ("none", "lrelu"):
+        raise ValueError("adain: act must be 'none' or 'lrelu'")
+
+
+def _adain_ws(N, HW, C, device):
+    nbytes = lib().vst_adain_ws_bytes(N, HW, C)
+    if nbytes == 0:
+        raise ValueError("adain: C = %d is not a multiple of 4 up to 1024" % C)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def adain_fwd(y, stats, h, act="none", slope=0.2):
+    """act((1 + gamma) * IN(y) + beta), {gamma, beta} = the halves of h[n] (vst_adain_fwd); h [N, 2*C] is the
+    style projection fc(s), stats from instnorm_stats."""
+    _adain_check(y, stats, h, act)
+    N, H, W, C = y.shape
+    out = torch.empty_like(y)
+    ws = torch.empty((N, C, 2), device=y.device)
+    _call("vst_adain_fwd", _p(y), _p(stats), _p(h), _p(out), _p(ws), N, H * W, C, ACT[act], float(slope), _stream())
+    return out
+
+
+def adain_bwd(g, y, stats, h, act="none", slope=0.2, dh=None, dbias=None, accumulate=False):
+    """dx of adain_fwd; dh [N, 2*C] and dbias [C] (the bias gradient of the conv that made y), each optional,
+    written or accumulated."""
+    _adain_check(y, stats, h, act)
+    _dev_check(g, dh, dbias)
+    N, H, W, C = y.shape
+    if g.shape != y.shape or (dh is not None and dh.shape != h.shape) or (dbias is not None and dbias.numel() != C):
+        raise ValueError("adain_bwd: g as y, dh as h, dbias [C]")
+    dx = torch.empty_like(y)
+    ws = _adain_ws(N, H * W, C, y.device)
+    _call("vst_adain_bwd", _p(g), _p(y), _p(stats), _p(h), _p(dx), _p(dh), _p(dbias), _p(ws), N, H * W, C, ACT[act],
+          float(slope), 1 if accumulate else 0, _stream())
+    return dx
+
+
+def act_fwd(x, act, slope=0.0):
+    """act(x) of a tensor whose element count is a multiple of 4 (vst_act_fwd; backward: act_bwd)."""
+    _dev_check(x)
+    y = torch.empty_like(x)
+    _call("vst_act_fwd", _p(x), _p(y), x.numel(), ACT[act], float(slope), _stream())
+    return y
+
+
+def avgpool2(x):
+    """F.avg_pool2d(x, 2) of NHWC x with even H and W (vst_avgpool2_fwd)."""
+    _dev_check(x)
+    N, H, W, C = x.shape
+    if H % 2 or W % 2 or C % 4:
+        raise ValueError("avgpool2: even H and W and C %% 4 == 0, got %s" % (tuple(x.shape),))
+    y = torch.empty((N, H // 2, W // 2, C), device=x.device)
+    _call("vst_avgpool2_fwd", _p(x), _p(y), N, H // 2, W // 2, C, _stream())
+    return y
+
+
+def avgpool2_bwd(gy):
+    _dev_check(gy)
+    N, H, W, C = gy.shape
+    gx = torch.empty((N, 2 * H, 2 * W, C), device=gy.device)
+    _call("vst_avgpool2_bwd", _p(gy), _p(gx), N, H, W, C, _stream())
+    return gx
+
+
+MERGE = {"same": 0, "pool": 1, "up": 2}  # VST_MERGE_*
+
+
+def _merge_b_shape(a_shape, mode):
+    N, H, W, C = a_shape
+    if mode not in MERGE:
+        raise ValueError("merge: mode must be one of %s" % sorted(MERGE))
+    if mode == "up" and (H % 2 or W % 2):
+        raise ValueError("merge 'up': a must have even H and W, got %s" % (tuple(a_shape),))
+    return {"same": (N, H, W, C), "pool": (N, 2 * H, 2 * W, C), "up": (N, H // 2, W // 2, C)}[mode]
+
+
+def merge(a, b, mode="same", scale=2 ** -0.5):
+    """(a + f(b)) * scale, NHWC (vst_merge_fwd): f = identity ('same'), avg_pool2d(., 2) ('pool': b at twice a's
+    resolution) or nearest 2x upsampling ('up': b at half a's resolution)."""
+    _dev_check(a, b)
+    if a.dim() != 4 or a.shape[-1] % 4 or tuple(b.shape) != _merge_b_shape(a.shape, mode):
+        raise ValueError("merge %r: a %s and b %s do not fit (C %% 4 == 0)" % (mode, tuple(a.shape), tuple(b.shape)))
+    lo = b if mode == "up" else a
+    out = torch.empty_like(a)
+    _call("vst_merge_fwd", _p(a), _p(b), _p(out), lo.shape[0], lo.shape[1], lo.shape[2], lo.shape[3], MERGE[mode],
+          float(scale), _stream())
+    return out
+
+
+def merge_bwd(g, mode="same", scale=2 ** -0.5):
+    """(ga, gb) of merge from out's gradient g, one pass over g (vst_merge_bwd)."""
+    _dev_check(g)
+    bs = _merge_b_shape(g.shape, mode)
+    ga, gb = torch.empty_like(g), torch.empty(bs, device=g.device)
+    lo = bs if mode == "up" else g.shape
+    _call("vst_merge_bwd", _p(g), _p(ga), _p(gb), lo[0], lo[1], lo[2], lo[3], MERGE[mode], float(scale), _stream())
+    return ga, gb
+
+
 def upsample2x(x):
     _dev_check(x)
     N, H, W, C = x.shape

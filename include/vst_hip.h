@@ -34,6 +34,9 @@
  *   vst_instnorm_affine_*       nn.InstanceNorm2d(affine=True) (+ReLU, + ResidualBlock layer_strength
  *                               gate) of methods/learning-based/network.py:147-298 (FastStyleNet)
  *   vst_cond_instnorm_*         ConditionalBatchNorm2d (+ReLU) of network.py:120-217 (FastStyleNet, n_styles > 1)
+ *   vst_adain_*                 AdaIN (+LeakyReLU) of StarGAN v2 core/model.py:67-120 (AdainResBlk)
+ *   vst_avgpool2_*, vst_merge_* F.avg_pool2d(., 2) and the (shortcut + residual) / sqrt(2) merge of ResBlk /
+ *                               AdainResBlk, core/model.py:23-120
  *   vst_instnorm_skip_*         UnetSkipConnectionBlock's skip concatenation with its in-place LeakyReLU / ReLU
  *                               (GAN-based networks.py:468-535; the unet_128 / unet_256 generators)
  *   vst_upsample2x_*            F.interpolate(scale_factor=2) in network.py:206-207
@@ -60,6 +63,8 @@ extern "C" {
 enum { VST_OK = 0, VST_EINVAL = 1, VST_EUNSUPPORTED = 2, VST_EHIP = 3 };
 enum { VST_PAD_ZERO = 0, VST_PAD_REFLECT = 1 };
 enum { VST_ACT_NONE = 0, VST_ACT_RELU = 1, VST_ACT_LRELU = 2, VST_ACT_TANH = 3 };
+/* vst_merge_*: how b meets a (same resolution | 2x2 mean of a b at twice it | nearest 2x of a b at half it) */
+enum { VST_MERGE_SAME = 0, VST_MERGE_POOL = 1, VST_MERGE_UP = 2 };
 enum { VST_PACK_KC = 0,   /* [R][S][Ci][Co]  (rows k=(r,s,ci), cols co) */
        VST_PACK_CK = 1,   /* [R][S][Co][Ci]  (rows k=(r,s,co), cols ci) */
        VST_PACK_OK = 2,   /* [Co][R][S][Ci]  conv forward B operand, k=(r,s,ci) contiguous per co */
@@ -513,6 +518,37 @@ int vst_cond_instnorm_bwd(const float* gy, const float* x, const float* stats, c
                           const float* embed, const float* bn_weight, const float* bn_bias, float* dx,
                           float* dembed, float* dbn_weight, float* dbn_bias, float* dbias, float* ws, int N,
                           int HW, int C, int Cl, int S, int act, int accumulate, void* stream);
+/* Adaptive instance norm (AdaIN, StarGAN v2 core/model.py:67-77): per sample n,
+ * y = act((1 + gamma) * xhat + beta), gamma = h[n][c], beta = h[n][C + c]; h [N][2*C] is the style projection
+ * fc(s), stats from vst_instnorm_stats.  x, y NHWC with C channels (a multiple of 4, at most 1024); act
+ * VST_ACT_NONE or VST_ACT_LRELU.  Folded per (n, c) into z = x * al + sh, al = (1 + gamma) * rstd,
+ * sh = beta - mean * al, tabulated by a coefficient kernel.  fwd: ws of at least N*C*2 floats (the head of a
+ * vst_adain_ws_bytes buffer serves).
+ * Backward: dx written; dh [N][2*C] (dgamma[n][c] = sum_p gz * xhat, dbeta[n][c] = sum_p gz, gz = gy * act'(z)) and
+ * dbias [C] (the gradient of a conv bias feeding the norm: the per-channel sum of dx) each may be NULL, and are
+ * written or accumulated (accumulate != 0).  All reductions fp64 in a fixed order over the slices and over n, no
+ * atomics: two runs are bit-equal.  ws: vst_adain_ws_bytes bytes (0 for a C the kernels do not take). */
+size_t vst_adain_ws_bytes(int N, int HW, int C);
+int vst_adain_fwd(const float* x, const float* stats, const float* h, float* y, float* ws, int N, int HW, int C,
+                  int act, float slope, void* stream);
+int vst_adain_bwd(const float* gy, const float* x, const float* stats, const float* h, float* dx, float* dh,
+                  float* dbias, float* ws, int N, int HW, int C, int act, float slope, int accumulate, void* stream);
+/* y = act(x) over n floats (n % 4 == 0): the standalone LeakyReLU of the pre-activation blocks; its backward is
+ * vst_act_bwd. */
+int vst_act_fwd(const float* x, float* y, long n, int act, float slope, void* stream);
+/* F.avg_pool2d(x, 2) on NHWC (C % 4 == 0): x [N][2H][2W][C] -> y [N][H][W][C] (H, W: the OUTPUT's size), the
+ * window summed in scan order then * 0.25; backward gx = gy / 4 on every pixel of the window. */
+int vst_avgpool2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
+int vst_avgpool2_bwd(const float* gy, float* gx, int N, int H, int W, int C, void* stream);
+/* The residual merge of ResBlk / AdainResBlk (core/model.py:62-64, :116-120): out = (a + f(b)) * scale, NHWC,
+ * C % 4 == 0.  mode VST_MERGE_SAME: f = identity, all [N][H][W][C].  VST_MERGE_POOL: f = avg_pool2d(., 2), a and out
+ * [N][H][W][C], b [N][2H][2W][C].  VST_MERGE_UP: f = nearest 2x upsampling, a and out [N][2H][2W][C], b [N][H][W][C].
+ * H, W are the LOW-resolution side's.  bwd: one read of g (out's shape); ga = scale * g (a's shape) and
+ * gb = scale * f^T(g) (b's shape) are both written.  64-bit element indices. */
+int vst_merge_fwd(const float* a, const float* b, float* out, int N, int H, int W, int C, int mode, float scale,
+                  void* stream);
+int vst_merge_bwd(const float* g, float* ga, float* gb, int N, int H, int W, int C, int mode, float scale,
+                  void* stream);
 /* U-Net skip connection (UnetSkipConnectionBlock.forward: cat([x, model(x)], 1) under the child's in-place
  * LeakyReLU(slope) and the parent's in-place ReLU).  y [N][HW][C] NHWC; z = (y - mean) * rstd with stats from
  * vst_instnorm_stats, or z = y when stats is NULL (the level below the outermost block, which has no norm).
