@@ -50,10 +50,10 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
   return i >= n ? 2 * n - 2 - i : i;
 }
 
-// The border rows of a ReflectionPad2d(1) + 3x3 data gradient (conv_bf.hip dgrad_border_pos: per
-// image NB = dgrad_border_rows rows of padded positions) that add into pixel (h, w): 0 for a pixel no
-// padded position mirrors onto, 1 for the single-target rows / columns, 3 for the four corner targets
-// (1 | H-2, 1 | W-2).  *b0 = the first such row.
+// Row map of the retired full-K border GEMM (per image NB rows of padded positions): the rows that add into
+// pixel (h, w): 0 for a pixel no padded position mirrors onto, 1 for the single-target rows / columns, 3 for
+// the four corner targets (1 | H-2, 1 | W-2).  *b0 = the first such row.  Reached only through the Ll == 0
+// arm of dgrad_border_slab_rows below, which no caller takes (see there).
 __host__ __device__ __forceinline__ int dgrad_border_rows_of(int h, int w, int H, int W, int* b0) {
   const int sw = W - 2, sh = H - 2, S4 = ((2 * sw + 2 * sh + 3) / 4) * 4;
   const bool rh = h == 1 || h == H - 2, rw = w == 1 || w == W - 2;
@@ -70,15 +70,13 @@ __host__ __device__ __forceinline__ int dgrad_border_rows_of(int h, int w, int H
   return 0;
 }
 
-// The border slabs' layout (conv_bf.hip bf_dgrad_refl1_slabs): ks split-K slabs of Mb rows; Ll == 0:
-// the full-K border rows, Lt = NB rows per image (dgrad_border_pos); else the K-restricted segments
-// top [0, Lt), bottom [Lt, 2Lt) (image n, column k: q = (-1 | H, k-1)), left [2Lt, 2Lt+Ll), right
-// [2Lt+Ll, 2Lt+2Ll) (image n, row k: q = (k, -1 | W)).
-struct BorderSlabs {
-  int ks, Mb, Lt, Ll;
-};
-
-// The slab rows that add into pixel (h, w) of image n, in summation order (<= 3; 0: none)
+// The border slabs of a ReflectionPad2d(1) + 3x3 data gradient (conv_bf.hip REFL 5): split-K slabs whose
+// rows are the padded positions q in four segments, top [0, Lt), bottom [Lt, 2Lt) (image n, column k:
+// q = (-1 | H, k-1)), left [2Lt, 2Lt+Ll), right [2Lt+Ll, 2Lt+2Ll) (image n, row k: q = (k, -1 | W)).
+// The slab rows that add into pixel (h, w) of image n, in summation order (<= 3; 0: none).
+// Every caller passes Ll >= 128 (bf_border5_plan), so the Ll == 0 arm never runs.  It is a run-time branch
+// inside dgrad_border5_add_k / dgrad_border5_add_inb_k: taking it out changes their instructions, which
+// the change that retired the full-K route left for a change with its own A/B.
 __host__ __device__ __forceinline__ int dgrad_border_slab_rows(int n, int h, int w, int H, int W, int Lt, int Ll,
                                                                int* rows) {
   if (Ll == 0) {
@@ -160,13 +158,11 @@ bool c4_direct_ok(int C, int Cop, int R, int S, int st, int Ho, int Wo, int math
 int c4_direct_launch(const float* x, const void* wsplit, long wps, const float* bias, float* y, int N, int H, int W,
                      int Ho, int Wo, int R, int S, int pad, int reflect, int act, float slope, int math, double* part,
                      hipStream_t s);
-// ReflectionPad2d(1) + 3x3 data gradient: interior GEMM + border-GEMM slabs (+ their add unless the
-// caller takes them: add_border = false)
+// ReflectionPad2d(1) + 3x3 data gradient: interior GEMM + border-GEMM slabs + their add
 bool bf_dgrad_refl1_ok(int N, int H, int W, int Cy, int Cx, int math);
 size_t bf_dgrad_refl1_ws_floats(int N, int H, int W, int Cy, int Cx, int math);
-size_t bf_dgrad_refl1_slabs(int N, int H, int W, int Cy, int Cx, int math, BorderSlabs* b);
 int bf_dgrad_refl1_launch(const float* dy, const void* wsplit, long wps, const float* addend, float* dx, int N, int H,
-                          int W, int Cy, int Cx, int math, hipStream_t s, float* ws, size_t ws_floats, bool add_border);
+                          int W, int Cy, int Cx, int math, hipStream_t s, float* ws, size_t ws_floats);
 // ... with the IN-backward partials of the layer below taken by the interior GEMM's epilogue and the border
 // add (vst_conv2d_dgrad_refl_in_epi): part [N][bf_dgrad_refl1_inb_slices][Cx][3] fp64
 bool bf_dgrad_refl1_inb_ok(int N, int H, int W, int Cy, int Cx, int math);

@@ -750,23 +750,12 @@ static int pick_splits(int tiles, int slots, int max_ns, int min_ns = 1) {
   return ns;
 }
 
-#ifndef VST_WG_BIG
-#define VST_WG_BIG 5  // rk tile kind of the wide (Cyp > 64, Mw >= 1024) weight gradients
-#endif
-#ifndef VST_WG_PADW
-#define VST_WG_PADW 1  // stride-1 x6 wgrads with Wo % 8 != 0 on the split-bf16 kernel via Wo-padded rows
-#endif
-#ifndef VST_WG_BIGM
-#define VST_WG_BIGM 512  // x6 wgrads with Cyp > 64 and Mw >= this run on 256x128 tiles (A/B: 1024 -> 512, -0.15 ms/step)
-#endif
-#ifndef VST_WG_BF
-#define VST_WG_BF 1   // x6 weight gradients on the split-bf16 kernel (conv_wgrad_bf_k)
-#endif
-
 static constexpr int g_wg_kind_s2 = -1;
 
 static WgradPlan plan_wgrad(int N, int H, int W, int Ho, int Wo, int Cx, int Cyp, int R, int S,
                             int stride, int math) {
+  constexpr int RK_WIDE_KIND = 5;  // rk tile kind of the wide (Cyp > 64, Mw >= 1024) x3 weight gradients
+  constexpr int BF_BIG_MW = 512;   // x6 wgrads with Cyp > 64 and Mw >= this run on 256x128 tiles (A/B: 1024 -> 512, -0.15 ms/step)
   WgradPlan p;
   p.Mw = R * S * Cx;
   p.trans = false;
@@ -783,13 +772,13 @@ static WgradPlan plan_wgrad(int N, int H, int W, int Ho, int Wo, int Cx, int Cyp
   const bool s2 = stride == 2 && W % 2 == 0;
   // stride 1 with Wo % 8 != 0 (PatchGAN's 31-wide layer): the output rows padded to a multiple of
   // 8 columns with zero dy (and zero x columns past the border), so 8-pixel chunks stay in one row
-  const int wpad = (s1 && Wo % 8 && Wo >= 8 && VST_WG_PADW) ? (8 - Wo % 8) : 0;
-  if (Cyp > 4 && (s1 || s2) && (Wo + wpad) % 8 == 0 && ov < 0 && math == VST_MATH_BF16X6 && VST_WG_BF) {
+  const int wpad = (s1 && Wo % 8 && Wo >= 8) ? (8 - Wo % 8) : 0;
+  if (Cyp > 4 && (s1 || s2) && (Wo + wpad) % 8 == 0 && ov < 0 && math == VST_MATH_BF16X6) {
     // x6: the split-bf16 weight-gradient kernel (conv_bf.hip), 256x128 tiles for the wide layers
     p.trans = p.bfk = true;
     p.pad = s1 ? pd2 / 2 : -1;
     p.wpad = wpad;
-    int kind = Cyp > 64 ? (p.Mw >= VST_WG_BIGM ? 7 : 3) : (p.Mw >= 1024 ? 1 : 8);
+    int kind = Cyp > 64 ? (p.Mw >= BF_BIG_MW ? 7 : 3) : (p.Mw >= 1024 ? 1 : 8);
     // M rows (tap, ci) that 256-row tiles pad more than 128-row ones (the generator's stride-2 3x3 layers:
     // 576 rows = 2.25 x 256, 1152 = 4.5 x 256) run on 128x128 tiles of 8 waves (64x32); round-5 sweep
     // (profiles/r05e_convT_wgrad_tiles.jsonl): 178 -> 172 / 149 -> 136 us at N = 8
@@ -814,7 +803,7 @@ static WgradPlan plan_wgrad(int N, int H, int W, int Ho, int Wo, int Cx, int Cyp
     p.pad = s1 ? pd2 / 2 : -1;
     // wide layers: 4 waves of 64x64 (two blocks per CU) under x3; under x6 the 128x128 image fits
     // one block per CU, so the 8-wave kind keeps two waves per SIMD
-    const int wide = math == VST_MATH_BF16X6 ? 0 : VST_WG_BIG;
+    const int wide = math == VST_MATH_BF16X6 ? 0 : RK_WIDE_KIND;
     int kind = (ov >= 0 && ov <= 6) ? ov : (Cyp <= 64 ? (p.Mw >= 1024 ? 2 : 3) : (p.Mw >= 1024 ? wide : 1));
     p.tile = (TileKind)kind;
     int bm, bn, bk, slots;

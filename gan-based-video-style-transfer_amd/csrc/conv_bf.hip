@@ -22,70 +22,6 @@
 
 #include "common.h"
 
-#ifndef VST_BF_X6K3
-#define VST_BF_X6K3 0
-#endif
-#ifndef VST_BF_MINB
-#define VST_BF_MINB 1
-#endif
-#ifndef VST_BF_X6_256
-#define VST_BF_X6_256 1
-#endif
-#ifndef VST_BF_KSLICE
-#define VST_BF_KSLICE 1
-#endif
-#ifndef VST_BF_TAIL_KIND
-#define VST_BF_TAIL_KIND 8
-#endif
-#ifndef VST_BF_TAIL
-#define VST_BF_TAIL 1
-#endif
-#ifndef VST_BF_SCHED
-#define VST_BF_SCHED 1
-#endif
-#ifndef VST_BF_PRIO
-#define VST_BF_PRIO 0
-#endif
-#ifndef VST_BF_MF16
-#define VST_BF_MF16 1
-#endif
-#ifndef VST_M16_STORE
-#define VST_M16_STORE 0  // M16 loop: stage store in group B (0) or group A (1)
-#endif
-#ifndef VST_M16_RDLO
-#define VST_M16_RDLO 0  // M16 loop: lo plane read in group B (0) or with hi in group A (1)
-#endif
-#ifndef VST_M16_SCHED
-#define VST_M16_SCHED 0  // M16 loop: sched_group_barrier filler pattern (0: compiler order)
-#endif
-#ifndef VST_M16_LOADFIRST
-#define VST_M16_LOADFIRST 0  // M16 loop: scheduling fence after group A (its global loads issue before group B's stores)
-#endif
-#ifndef VST_M16_PRIO
-#define VST_M16_PRIO 0  // M16 loop: s_setprio 1 for the second-dispatched half of the waves
-#endif
-#ifndef VST_M16_LOADEARLY
-#define VST_M16_LOADEARLY 0  // M16 loop: the next stages' loads first in the step, fenced
-#endif
-#ifndef VST_BF_SPLITK
-#define VST_BF_SPLITK 1  // split-K wave-quantisation tails (when the caller passes a workspace)
-#endif
-#ifndef VST_BF_FULLSPLIT_MAX
-#define VST_BF_FULLSPLIT_MAX 128  // x6 forwards of at most this many 256x128 tiles run whole as split-K
-#endif
-#ifndef VST_BF_TAIL_FORCE
-#define VST_BF_TAIL_FORCE -1
-#endif
-#ifndef VST_WG_SELECT
-#define VST_WG_SELECT 1
-#endif
-#ifndef VST_BF_STORE_LATE
-#define VST_BF_STORE_LATE 0
-#endif
-#ifndef VST_BF_LDS_EPI
-#define VST_BF_LDS_EPI 0  // M16 forward epilogue: tile staged through LDS, stored as whole float4 rows
-#endif
-
 namespace vst {
 namespace bf {
 
@@ -115,7 +51,7 @@ struct Tile {
   // M16 (x6, BK 32, 64-deep wave tiles): the products run on v_mfma_f32_16x16x32_bf16 (16x16
   // blocks, one 32-deep k step per stage) instead of 32x32x16 — the same cycles per FLOP, but the
   // chip holds a higher clock on it under load (MI355X_MICROARCH.md, DVFS item 7).
-  static constexpr bool M16 = VST_BF_MF16 && NP == 3 && BK == 32 && WM % 32 == 0 && WN % 32 == 0;
+  static constexpr bool M16 = NP == 3 && BK == 32 && WM % 32 == 0 && WN % 32 == 0;
   static constexpr int MI16 = WM / 16, NI16 = WN / 16;
   // chunk XOR of a row's 16-B chunks: row group q = (row >> SWS) & (KC - 1).  The 16x16x32 reads
   // (lane: row l & 15, chunk l >> 4) are conflict-free for the ds_read_b128 lane groups
@@ -127,11 +63,7 @@ struct Tile {
   }
   // co-resident blocks per CU the register budget is compiled for: two when two double-buffered
   // stage pairs fit the 160 KB LDS, else one (then each wave may use the whole 2-wave budget)
-#if VST_BF_MINB
   static constexpr int MINB = 4 * STAGE <= 160 * 1024 ? 2 : 1;
-#else
-  static constexpr int MINB = 2;
-#endif
 };
 
 template <class T>
@@ -157,13 +89,10 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {
 #ifndef VST_BF_FAKE_ZA
 #define VST_BF_FAKE_ZA 0  // developer timing experiment only: every A gather reads the zero page (WRONG results)
 #endif
-#ifndef VST_BF_FAKE_ADMA
-#define VST_BF_FAKE_ADMA 0  // developer timing experiment only: A LDS-DMA'd from x's own bytes (WRONG results)
-#endif
 #ifndef VST_BF_FAKE_ZB
 #define VST_BF_FAKE_ZB 0  // developer timing experiment only: every B load reads the zero page (WRONG results)
 #endif
-#if (VST_BF_FAKESPLIT || VST_BF_FAKE16 || VST_BF_FAKE_ZA || VST_BF_FAKE_ZB || VST_BF_FAKE_ADMA) && !defined(VST_DEV_VARIANT)
+#if (VST_BF_FAKESPLIT || VST_BF_FAKE16 || VST_BF_FAKE_ZA || VST_BF_FAKE_ZB) && !defined(VST_DEV_VARIANT)
 #error "VST_BF_FAKESPLIT / VST_BF_FAKE16 are developer-only timing modes (wrong results): build them with tools/build_variant.py"
 #endif
 template <int NP>
@@ -249,10 +178,6 @@ __device__ __forceinline__ void mma_frag(const Frag<T>& f, f32x16 (&acc)[T::MI][
 
 // Stage writer: A rows as fp32 pairs (split here), B rows as pre-split planes.  Masked rows were
 // loaded from the zero page, so every row is written unconditionally.
-#ifndef VST_BF_GLDS_B
-#define VST_BF_GLDS_B 1  // x6 M16 KSL forwards: the pre-split B operand LDS-DMA'd (global_load_lds_dwordx4)
-                         // instead of register-staged
-#endif
 template <class T>
 __device__ __forceinline__ void store_stage(char* st, const float4 (&ra)[T::A_LD][2],
                                             const u32x4_t (&rbv)[T::B_LD][T::NP], int rb, int kq,
@@ -276,33 +201,20 @@ __device__ __forceinline__ void store_stage(char* st, const float4 (&ra)[T::A_LD
   }
 }
 
-// Issue pattern of one k group's MFMAs (VST_BF_SCHED): each MFMA is followed by a share of the
-// group's other work, so the fragment reads, global loads, the split VALU and its ds_writes sit
-// in the MFMA gaps instead of in blocks the matrix pipe waits behind.  first: the group that also
-// issues the next loads and the stage store; the group after the barrier only reads fragments.
+// Issue pattern of a k group's MFMAs that only has fragment reads beside it: each MFMA is followed
+// by one ds_read_b128 and two VALU, so the reads sit in the MFMA gaps instead of in a block the
+// matrix pipe waits behind.  The stage's first group (before the barrier), which also issues the
+// next loads, the split and the stage store, is left in compiler order.
 template <class T>
 __device__ __forceinline__ void sched_group(bool first, bool after_barrier) {
   constexpr int NM = T::MI * T::NI * (T::NP == 3 ? 6 : 3) * (VST_BF_FAKE16 ? 2 : 1);  // MFMAs per k group
   constexpr int NR = T::NP * (T::MI + T::NI);                   // ds_read_b128 per k group
-  constexpr int NV = T::A_LD * 2 + T::B_LD * T::NP;             // global loads per stage
-  constexpr int NW = T::A_LD * T::NP + T::B_LD * T::NP;         // ds_write_b128 per stage
-  if (first && !after_barrier) {
-    if (VST_BF_SCHED < 2) return;
+  if (first && !after_barrier) return;
 #pragma unroll
-    for (int i = 0; i < NM; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // MFMA
-      if (i < NR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-      if (i < NV) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
-      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);          // VALU
-      if (i >= NM - NW - 1 && i < NM - 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < NM; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      if (i < NR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-    }
+  for (int i = 0; i < NM; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);              // MFMA
+    if (i < NR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);              // VALU
   }
 }
 
@@ -328,9 +240,6 @@ __device__ __forceinline__ void main_loop(char* smem, int nk, f32x16 (&acc)[T::M
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm0 = (wave / T::WAVES_N) * T::WM, wn0 = (wave % T::WAVES_N) * T::WN;
   if (nk <= 0) return;
-  // second-dispatched half of the waves: static priority 1 (it otherwise loses every issue
-  // arbitration to its older partner on the SIMD; MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  if (VST_BF_PRIO && wave >= T::NW / 2) __builtin_amdgcn_s_setprio(1);
   load_all(0);
   prep(0);
   store_stage<T>(smem, ra[0], rbv[0], rb, kq);
@@ -350,22 +259,16 @@ __device__ __forceinline__ void main_loop(char* smem, int nk, f32x16 (&acc)[T::M
       if (g == 0) {
         adv(kt + 2 < nk);
         load_all(P);
-        if (!VST_BF_STORE_LATE) {
-          prep(P ^ 1);
-          store_stage<T>(nxt, ra[P ^ 1], rbv[P ^ 1], rb, kq);
-        }
+        prep(P ^ 1);
+        store_stage<T>(nxt, ra[P ^ 1], rbv[P ^ 1], rb, kq);
       }
       if (g == G - 1) {
-        if (VST_BF_STORE_LATE) {
-          prep(P ^ 1);
-          store_stage<T>(nxt, ra[P ^ 1], rbv[P ^ 1], rb, kq);
-        }
         __builtin_amdgcn_sched_barrier(0);  // keep this group's MFMAs after the barrier (they cover the read)
         __syncthreads();
         read_frag<T>(fr[fi ^ 1], nxt, 0, wm0, wn0, lane);
       }
       mma_frag<T>(fr[fi], acc);
-      if (VST_BF_SCHED) sched_group<T>(g == 0, g == G - 1);
+      sched_group<T>(g == 0, g == G - 1);
     }
   };
   int kt = 0;
@@ -407,20 +310,6 @@ __device__ __forceinline__ void mma16(const Plane16<T>& A, const Plane16<T>& B, 
       acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A.a[i], B.b[j], acc[i][j], 0, 0, 0);
 }
 
-// Fillers of an M16 group: every MFMA followed by its share of the group's reads / loads / VALU /
-// ds_writes (the same idea as sched_group).
-template <int NM, int NR, int NV, int NVALU, int NW>
-__device__ __forceinline__ void sched16() {
-#pragma unroll
-  for (int i = 0; i < NM; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    if (i < NR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    if (i < NV) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-    if (NVALU) __builtin_amdgcn_sched_group_barrier(0x002, NVALU, 0);
-    if (i >= NM - NW - 1 && i < NM - 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-  }
-}
-
 // K loop of the M16 tiles.  The three planes are consumed in three groups per stage so that only
 // three plane sets are ever live (as the 32x32x16 loop's two k-group sets):
 //   A: (mid, mid)                        read hi of this stage; global loads of stage kt + 2
@@ -440,7 +329,7 @@ struct DmaB {
 };
 typedef __attribute__((address_space(3))) void lds_void;
 
-// dmab(stage): VST_BF_GLDS_B's LDS-DMA of the B operand of the stage the K cursor points at into that
+// dmab(stage): the LDS-DMA of the B operand of the stage the K cursor points at into that
 // stage's LDS image (a no-op otherwise), issued at the prologue and at the start of every step.
 template <class T, class LoadAll, class Adv, class Prep, class DmaB>
 __device__ __forceinline__ void main_loop16(char* smem, int nk, f32x4v (&acc)[T::MI16][T::NI16],
@@ -449,9 +338,6 @@ __device__ __forceinline__ void main_loop16(char* smem, int nk, f32x4v (&acc)[T:
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm0 = (wave / T::WAVES_N) * T::WM, wn0 = (wave % T::WAVES_N) * T::WN;
   if (nk <= 0) return;
-  constexpr int NM = T::MI16 * T::NI16, NR = T::MI16 + T::NI16;
-  constexpr int NV = T::A_LD * 2 + T::B_LD * T::NP, NW = T::A_LD * T::NP + T::B_LD * T::NP;
-  if (VST_M16_PRIO && wave >= T::NW / 2) __builtin_amdgcn_s_setprio(1);
   dmab(smem);
   load_all(0);
   prep(0);
@@ -465,41 +351,25 @@ __device__ __forceinline__ void main_loop16(char* smem, int nk, f32x4v (&acc)[T:
     constexpr int P = decltype(par)::value;
     const char* cur = smem + P * T::STAGE;
     char* nxt = smem + (P ^ 1) * T::STAGE;
-    constexpr bool SA = VST_M16_STORE == 1, RA = VST_M16_RDLO == 1;
     dmab(nxt);  // the cursor is on stage kt + 1 here (adv below moves it to kt + 2)
-    if (VST_M16_LOADEARLY) {
-      adv(kt + 2 < nk);
-      load_all(P);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    // group A
     read_plane16<T>(hi, cur, 0, wm0, wn0, lane);
-    if (RA) read_plane16<T>(lo, cur, 2, wm0, wn0, lane);
-    if (!VST_M16_LOADEARLY) {
-      adv(kt + 2 < nk);
-      load_all(P);
-    }
-    if (SA) {
-      prep(P ^ 1);
-      store_stage<T>(nxt, ra[P ^ 1], rbv[P ^ 1], rb, kq, !dmab.active, !dmab.a_active);
-    }
+    adv(kt + 2 < nk);
+    load_all(P);
     mma16<T>(mid, mid, acc);
-    if (VST_M16_SCHED) sched16<NM, RA ? 2 * NR : NR, NV, SA ? 4 : 0, SA ? NW : 0>();
-    if (VST_M16_LOADFIRST) __builtin_amdgcn_sched_barrier(0);
-    if (!RA) read_plane16<T>(lo, cur, 2, wm0, wn0, lane);
-    if (!SA) {
-      prep(P ^ 1);
-      store_stage<T>(nxt, ra[P ^ 1], rbv[P ^ 1], rb, kq, !dmab.active, !dmab.a_active);
-    }
+    // group B
+    read_plane16<T>(lo, cur, 2, wm0, wn0, lane);
+    prep(P ^ 1);
+    store_stage<T>(nxt, ra[P ^ 1], rbv[P ^ 1], rb, kq, !dmab.active, !dmab.a_active);
     mma16<T>(mid, hi, acc);
     mma16<T>(hi, mid, acc);
-    if (VST_M16_SCHED) sched16<2 * NM, RA ? 0 : NR, 0, SA ? 0 : 2, SA ? 0 : NW>();
+    // group C
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
     read_plane16<T>(mid, nxt, 1, wm0, wn0, lane);
     mma16<T>(hi, hi, acc);
     mma16<T>(lo, hi, acc);
     mma16<T>(hi, lo, acc);
-    if (VST_M16_SCHED) sched16<3 * NM, NR, 0, 0, 0>();
   };
   int kt = 0;
   for (; kt + 1 < nk; kt += 2) {
@@ -573,86 +443,9 @@ __device__ __forceinline__ void inb_term(float g, float z, float mean, float rst
 // dxp = the full correlation of dy with the rotated taps (a 3x3 conv of dy with zero padding 2).
 // The interior term dxp(j), j in H x W, is the zero-pad-1 forward conv over dy (one exact grid: for
 // N = 8 at 64 x 64 the 256x128 tiles make one whole CU round).  The 2(H+W)+4 padded border
-// positions q add into the rows / columns 1 and H-2 / W-2: this map orders them per image as
-//   rows [0, S):   single targets — top (q = (-1, w)), bottom (q = (H, w)) for w not in {1, W-2},
-//                  then left (q = (h, -1)), right (q = (h, W)) for h not in {1, H-2};
-//   rows [S, S4):  padding to a multiple of 4 (no position);
-//   rows S4 + 4g + {0, 1, 2}: the three positions of corner target g (g: (1,1), (1,W-2), (H-2,1),
-//                  (H-2,W-2)), + 4g + 3 none — a 4-row group sits in one lane's accumulator rows.
-// S = 2 (W - 2) + 2 (H - 2), S4 = S rounded up to a multiple of 4, rows per image S4 + 16.
-// (qh, qw) = the padded position (-100 for none: every tap gathers zeros), (th, tw) its target.
-__host__ __device__ __forceinline__ int dgrad_border_rows(int H, int W) {
-  return ((2 * (W - 2) + 2 * (H - 2) + 3) / 4) * 4 + 16;
-}
-
-__host__ __device__ __forceinline__ void dgrad_border_pos(int b, int H, int W, int& qh, int& qw, int& th, int& tw) {
-  const int sw = W - 2, sh = H - 2, S = 2 * sw + 2 * sh, S4 = (S + 3) / 4 * 4;
-  qh = qw = th = tw = -100;
-  if (b < 2 * sw) {  // top / bottom
-    const int k = b < sw ? b : b - sw;
-    tw = k == 0 ? 0 : (k == sw - 1 ? W - 1 : k + 1);
-    qw = tw;
-    qh = b < sw ? -1 : H;
-    th = b < sw ? 1 : H - 2;
-    return;
-  }
-  if (b < S) {  // left / right
-    const int b2 = b - 2 * sw, k = b2 < sh ? b2 : b2 - sh;
-    th = k == 0 ? 0 : (k == sh - 1 ? H - 1 : k + 1);
-    qh = th;
-    qw = b2 < sh ? -1 : W;
-    tw = b2 < sh ? 1 : W - 2;
-    return;
-  }
-  if (b < S4) return;
-  const int g = (b - S4) >> 2, r = (b - S4) & 3;
-  if (r == 3) return;
-  const int top = g < 2, left = (g & 1) == 0;
-  th = top ? 1 : H - 2;
-  tw = left ? 1 : W - 2;
-  const int ph = top ? -1 : H, pw = left ? -1 : W;  // the out-of-frame row / column
-  if (r == 0) { qh = ph; qw = tw; }
-  else if (r == 1) { qh = ph; qw = pw; }
-  else { qh = th; qw = pw; }
-}
-
-// dx[n][th][tw][c] += the border rows' GEMM result (split slabs summed in order); a corner target's
-// three rows are summed in row order by one thread.  grid (ceil(N*NB / 16), ceil(C / 64)): thread
-// (one of 16 rows, 4-channel group); every dx element has exactly one writer.  The slab loads of a
-// row are issued together (up to 16 splits in flight per thread).
-__global__ __launch_bounds__(256) void dgrad_border_add_k(const float* __restrict__ slab, int ks, int Mb, int C,
-                                                          float* __restrict__ dx, int H, int W, int NB) {
-  const int t = threadIdx.x;
-  const int c = blockIdx.y * 64 + (t & 15) * 4;
-  const int m = blockIdx.x * 16 + (t >> 4);
-  if (m >= Mb || c >= C) return;
-  const int n = m / NB, b = m - n * NB;
-  int qh, qw, th, tw;
-  dgrad_border_pos(b, H, W, qh, qw, th, tw);
-  if (th < 0) return;
-  const int S4 = NB - 16;
-  if (b >= S4 && ((b - S4) & 3) != 0) return;
-  const int nr = b >= S4 ? 3 : 1;
-  const long zst = (long)Mb * C;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int r = 0; r < nr; ++r) {
-    const float* base = slab + (long)(m + r) * C + c;
-    float4 u[16];
-#pragma unroll
-    for (int z = 0; z < 16; ++z)
-      if (z < ks) u[z] = *reinterpret_cast<const float4*>(base + z * zst);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int z = 0; z < 16; ++z)
-      if (z < ks) add_f4(acc, u[z]);
-    add_f4(v, acc);
-  }
-  float4* d = reinterpret_cast<float4*>(dx + (((long)n * H + th) * W + tw) * C + c);
-  float4 o = *d;
-  add_f4(o, v);
-  *d = o;
-}
-
+// positions q add into the rows / columns 1 and H-2 / W-2; a corner target (1 | H-2, 1 | W-2) takes
+// three of them.
+//
 // The K-restricted border GEMM (conv_fprop_bf_k REFL 5): the padded positions as four segments of
 // rows, each padded to a whole number of M-tiles:
 //   top    [0, Lt):            image n, k in [0, W+2): q = (-1, k-1)  (the two corners included)
@@ -837,6 +630,9 @@ __device__ __attribute__((aligned(256))) float g_zero_page[64];
 // 3 channels + 1 zero): a thread's 8-deep K chunk then spans two taps, the second one's rows have
 // their own offsets (aoff2), and a K that ends half-way through a chunk (R*S odd) reads zeros for the
 // missing tap.  K = R*S*4 instead of R*S*8 with the input padded to 8 channels: half the MFMA work.
+// 5 = the K-restricted border rows of a reflect-pad-1 data gradient (border5_seg_rows; split-K slabs
+// only).  There is no 4: it was the full-K border rows, and the number stays unused so that the
+// kernels' symbols keep their names.
 // SPLIT (KSL only): split-K over the K-steps — block L = z * tiles + tile runs K-steps
 // [z * spk, z * spk + spk) and stores its raw partial tile to slab[z][m - m_base][Cop]
 // (fprop_splitk_reduce_k sums the splits in order and applies bias / act / IN partials).
@@ -849,7 +645,7 @@ __device__ __forceinline__ void conv_fprop_bf_body(
     int spk, float* __restrict__ slab, const float* __restrict__ addend, int oph,
     InbArgs inb = InbArgs{}, const __bf16* __restrict__ apl = nullptr, long pps = 0) {
   static_assert(!SPLIT || KSL, "split-K needs the channel-slice-major K walk");
-  static_assert(REFL < 4 || (SPLIT && KSL), "border rows run as split-K slabs");
+  static_assert((REFL >= 0 && REFL <= 3) || (REFL == 5 && SPLIT && KSL), "REFL 5 (border rows) runs as split-K slabs");
   __shared__ __attribute__((aligned(16))) char smem[2 * T::STAGE];
   constexpr int A_LD = T::A_LD, B_LD = T::B_LD, RPP = T::RPP, NP = T::NP;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -881,16 +677,6 @@ __device__ __forceinline__ void conv_fprop_bf_body(
       hb[j] = !live ? -1000000 : (seg == 0 ? 0 : (seg == 1 ? H - 1 : k - 1));
       wb[j] = seg < 2 ? k - 2 : (seg == 2 ? 0 : W - 1);
       pb[j] = live ? n * H * W * C : 0;
-      continue;
-    }
-    if constexpr (REFL == 4) {
-      // border rows of a reflect-pad-1 data gradient (dgrad_border_pos): Wo = rows per image
-      const int n = mm / Wo;
-      int qh, qw, th, tw;
-      dgrad_border_pos(mm - n * Wo, H, W, qh, qw, th, tw);
-      hb[j] = qh - padh;
-      wb[j] = qw - padw;
-      pb[j] = n * H * W * C;
       continue;
     }
     const int hw = Ho * Wo;
@@ -959,17 +745,16 @@ __device__ __forceinline__ void conv_fprop_bf_body(
 
   float4 ra[2][A_LD][2];
   u32x4_t rbv[2][B_LD][NP];
-  constexpr bool GLDS = VST_BF_GLDS_B && T::M16 && KSL && !C4 && REFL != 5;
+  // GLDS (the x6 M16 channel-slice kernels): the pre-split B operand LDS-DMA'd (global_load_lds_dwordx4)
+  // instead of register-staged
+  constexpr bool GLDS = T::M16 && KSL && !C4 && REFL != 5;
   // APRE: the A operand arrives pre-split (apl: three bf16 planes of x's NHWC layout, plane stride pps
-  // elements) by LDS-DMA like B — no fp32 A image, no split in the staging.  VST_BF_FAKE_ADMA (developer timing
-  // only, WRONG results): every GLDS kernel DMAs A from x's own bytes read as planes.
-  constexpr bool GLDS_A = (APRE || VST_BF_FAKE_ADMA) && GLDS;
+  // elements) by LDS-DMA like B — no fp32 A image, no split in the staging.
+  constexpr bool GLDS_A = APRE && GLDS;
   // APRE without the DMA (the K-restricted border GEMM, REFL 5): A's planes loaded into registers and put back
   // together as fp32 (hi + mid + lo is the value exactly), then staged as usual — the same planes in LDS
   constexpr bool APRE_REG = APRE && !GLDS_A;
   static_assert(!APRE || GLDS_A || REFL == 5, "pre-split A: the x6 M16 channel-slice kernels with LDS-DMA B, or REFL 5");
-  const __bf16* apl_ = VST_BF_FAKE_ADMA ? reinterpret_cast<const __bf16*>(x) : apl;
-  const long pps_ = VST_BF_FAKE_ADMA ? (long)(M / (Ho * Wo)) * H * W * C / 2 : pps;
   auto load_all = [&](int set) __attribute__((always_inline)) {
     const bool kin = KSL || kcur < Ktot;  // the K tail reads zeros (A) against row 0 (B)
     const int ka = KSL ? ksb + kq8 : kc;
@@ -1039,12 +824,12 @@ __device__ __forceinline__ void conv_fprop_bf_body(
                                 : (VST_BF_FAKE_ZB == 2 ? ws : wrow[j]) + p * wps + kb);  // 2: weight row 0 for every row
     }
   };
-  // VST_BF_GLDS_B: the B image of the stage the cursor is on, one global_load_lds_dwordx4 per (row
+  // GLDS: the B image of the stage the cursor is on, one global_load_lds_dwordx4 per (row
   // block, plane) and wave — a wave fills 16 whole 64-B rows (1 KiB, lane-linear): lane l's 16 B land
   // at row 16 w + l / 4, slot l % 4, so it reads source chunk (l % 4) ^ swz(row) (the LDS image's
   // chunk swizzle applied on the source address)
   auto dma_b = [&](char* st) __attribute__((always_inline)) {
-    if constexpr (GLDS_A) {  // the A rows of the stage (row rb + RPP j: this thread's aoff[j]), planes apl_
+    if constexpr (GLDS_A) {  // the A rows of the stage (row rb + RPP j: this thread's aoff[j]), planes apl
       const __bf16* zb = reinterpret_cast<const __bf16*>(zp);
 #pragma unroll
       for (int j = 0; j < A_LD; ++j) {
@@ -1052,11 +837,11 @@ __device__ __forceinline__ void conv_fprop_bf_body(
         const int csrc = (t % T::KC) ^ T::swz(row);
         const int wrow0 = __builtin_amdgcn_readfirstlane(row - (lane / T::KC));
         const bool live = aoff[j] >= 0;
-        const __bf16* src = live ? apl_ + aoff[j] + ksb + 8 * csrc : zb + 8 * csrc;
+        const __bf16* src = live ? apl + aoff[j] + ksb + 8 * csrc : zb + 8 * csrc;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-          __builtin_amdgcn_global_load_lds(src + (live ? p * pps_ : 0), (lds_void*)(st + p * T::A_PLANE + wrow0 * T::ROWB),
+          __builtin_amdgcn_global_load_lds(src + (live ? p * pps : 0), (lds_void*)(st + p * T::A_PLANE + wrow0 * T::ROWB),
                                            16, 0, 0);
 #endif
         }
@@ -1131,12 +916,12 @@ __device__ __forceinline__ void conv_fprop_bf_body(
     // 16x16 blocks: lane holds column lane & 15, rows 4 (lane >> 4) + r.  IN partials per 32-row
     // group (block pair 2g, 2g+1): per-lane fixed-order fp64 sums, then over the four lanes of a
     // column (xor 16, xor 32).
-    // LDS_EPI: the activated tile goes to LDS (row stride BN + 16 floats: the two rows of a 32-lane
+    // LEPI: the activated tile goes to LDS (row stride BN + 16 floats: the two rows of a 32-lane
     // write group land 16 banks apart) and leaves as whole float4 rows (coalesced stores).
     // (an addend — the residual gradient of a data gradient — is always added on this path: its float4
     // loads ride with the row stores instead of 4-byte reads per accumulator element)
     constexpr bool LFIT = T::BM * (T::BN + 16) * 4 <= 2 * T::STAGE;
-    const bool LEPI = LFIT && (VST_BF_LDS_EPI || addend != nullptr || oph != 0 || inb.part != nullptr);
+    const bool LEPI = LFIT && (addend != nullptr || oph != 0 || inb.part != nullptr);
     constexpr int LDE = T::BN + 16;
     float* ept = reinterpret_cast<float*>(smem);
     // InbArgs: the IN input z (and the addend) of the wave's 32-row group (wave w: rows 32 w .., one group per
@@ -1469,7 +1254,7 @@ __global__ __launch_bounds__(T::NT, T::MINB) void conv_wgrad_bf_k(
   };
   const long row_step = (long)st * Wp - Wo, img_step = (long)(Hp - st * Ho) * Wp;
   auto adv = [&](bool go) __attribute__((always_inline)) {
-    if (W1 && VST_WG_SELECT) {
+    if (W1) {
       const int pw1 = pwo + T::BK;
       const bool e1 = pw1 >= Wo;
       const int ph1 = pho + (e1 ? 1 : 0);
@@ -2082,13 +1867,17 @@ static void bf_geom(int kind, int np, int* bm, int* bn, int* slots) {
   *slots = sl < 1 ? 1 : sl;
 }
 
+// x6 forwards of at most this many 256x128 tiles run whole as split-K (bf_split_plan's "full" form;
+// bf_plan keeps its partial-round 256x128 plan off them)
+constexpr int BF_FULLSPLIT_MAX = 128;
+
 // Launch plan of the split-arithmetic forward for an M x Cop output: the tile kind of the main
 // launch and, when the grid is split for wave quantisation, the first pixel row of the tail launch
 // (0 = one launch) and the tail's tile kind.  Host-only; exported through vst_conv_plan_fwd.
 void bf_plan(long M, int Cop, int math, int kind, int* kind_out, int* m_split_out, int* tail_out) {
   int kd = bf_pick(M, Cop, kind);
-  int m_split = 0, tail_kind = VST_BF_TAIL_KIND;
-#if VST_BF_X6_256
+  constexpr int X3_TAIL_KIND = 8;  // the x3 wave-quantisation tail's tile: 64x64
+  int m_split = 0, tail_kind = X3_TAIL_KIND;
   // x6 runs one 128x128 or 256x128 block per CU either way (the three-plane stage pairs are 96 /
   // 144 KB): 256x128 tiles of 8 waves x (64x64) halve the LDS fragment reads per MFMA and the
   // barriers per FLOP.  Whole rounds of 256 blocks run as one launch; otherwise the whole rounds
@@ -2116,13 +1905,12 @@ void bf_plan(long M, int Cop, int math, int kind, int* kind_out, int* m_split_ou
         const double cost = (double)(ms / 256 * nt) / VST_NUM_CUS + rounds * (bm * bn) / (256.0 * 128.0) / eff[c];
         if (cost < best - 1e-9) { best = cost; bk = cand[c]; }
       }
-      if (VST_BF_TAIL_FORCE >= 0) bk = VST_BF_TAIL_FORCE;  // developer A/B of the tail tile
       kd = 7;
       if (bk >= 0) {
         m_split = (int)ms;
         tail_kind = bk;
       }
-    } else if (b256 < VST_NUM_CUS && b256 > VST_BF_FULLSPLIT_MAX) {
+    } else if (b256 < VST_NUM_CUS && b256 > BF_FULLSPLIT_MAX) {
       // one partial round of 256x128 tiles (more than the all-split form takes) against the 128x128 grid's
       // rounds at the same one block per CU (a 32-deep K step ~2.25 vs ~1.5 us): the 436x1024 ResnetBlocks
       // (M = 27904, 218 tiles) ran 436 128x128 blocks = 2 rounds
@@ -2130,8 +1918,6 @@ void bf_plan(long M, int Cop, int math, int kind, int* kind_out, int* m_split_ou
       if (2.25 < 1.5 * r128) kd = 7;
     }
   }
-#endif
-#if VST_BF_TAIL
   // Wave quantisation: 128x128 x3 blocks run two per CU, so a grid a few tiles past a whole
   // number of blocks per CU (the padded-frame dgrad: 546 = 2 x 256 + 34 blocks at N = 8) keeps
   // most CUs idle for one extra block time.  Such a tail (<= 1/4 of the CUs) runs as a second
@@ -2141,10 +1927,9 @@ void bf_plan(long M, int Cop, int math, int kind, int* kind_out, int* m_split_ou
     const long per = blocks / VST_NUM_CUS, tail = blocks - per * VST_NUM_CUS;
     if (per >= 1 && tail > 0 && 4 * tail <= VST_NUM_CUS && (per * VST_NUM_CUS) % nt == 0) {
       m_split = (int)(per * VST_NUM_CUS / nt) * 128;
-      tail_kind = VST_BF_TAIL_KIND;
+      tail_kind = X3_TAIL_KIND;
     }
   }
-#endif
   *kind_out = kd;
   *m_split_out = m_split;
   *tail_out = m_split ? tail_kind : -1;
@@ -2176,13 +1961,13 @@ int bf_tail_ks(long M, int Cop, int m_split, int nk) {
 
 // Split-K plan of an x6 forward with a workspace: (first split row, splits), splits = 0 for none.
 //   * tail: a whole-round 256x128 plan with a partial last round -> that round as splits (bf_tail_ks);
-//   * full: a grid of at most VST_BF_FULLSPLIT_MAX 256x128 tiles (the PatchGAN layers, half-batch
+//   * full: a grid of at most BF_FULLSPLIT_MAX 256x128 tiles (the PatchGAN layers, half-batch
 //     passes) -> the whole conv as ks K-range splits of 256x128 tiles filling the CUs, instead of
 //     small tiles that cannot fill them either; same cost model.
 void bf_split_plan(long M, int Cop, int C, int R, int S, int math, int kind, int* m_first, int* ks_out) {
   *m_first = 0;
   *ks_out = 0;
-  if (math != VST_MATH_BF16X6 || !VST_BF_KSLICE || C % 32 || !VST_BF_SPLITK || kind >= 0) return;
+  if (math != VST_MATH_BF16X6 || C % 32 || kind >= 0) return;
   const int nk = (R * S * C + 31) / 32;
   int kd, m_split, tail_kind;
   bf_plan(M, Cop, math, -1, &kd, &m_split, &tail_kind);
@@ -2192,7 +1977,7 @@ void bf_split_plan(long M, int Cop, int C, int R, int S, int math, int kind, int
     return;
   }
   const long b256 = ((M + 255) / 256) * ((Cop + 127) / 128);
-  if (kd == 7 || b256 > VST_BF_FULLSPLIT_MAX) return;
+  if (kd == 7 || b256 > BF_FULLSPLIT_MAX) return;
   // the small-tile plan it would replace: rounds x K-steps x the tile's per-round K-step time (x6,
   // 16x16x32; measured on the ResnetBlock / PatchGAN shapes: 256x128 2.25 us, 128x128 1.5 us,
   // 64x128 at two per CU 1.8 us; the 64-wide tiles assumed 1.2 us)
@@ -2255,11 +2040,11 @@ int bf_fprop_launch(const float* x, const void* wsplit, long wps, const float* b
       hipLaunchKernelGGL((bf::conv_fprop_bf_k<T, false, 3>), grid, dim3(T::NT), 0, s, x, ws, wps, bias, y, \
                          H, W, C, Ho, Wo, Cop, S, st, padh, padw, reflect, act, slope, Mend, K, mb, part, 0,      \
                          nullptr, addend, oph);                                                          \
-    else if (VST_BF_KSLICE && C % BK_ == 0 && reflect)                                              \
+    else if (C % BK_ == 0 && reflect)                                                               \
       hipLaunchKernelGGL((bf::conv_fprop_bf_k<T, true, 1>), grid, dim3(T::NT), 0, s, x, ws, wps, bias, y, \
                          H, W, C, Ho, Wo, Cop, S, st, padh, padw, reflect, act, slope, Mend, K, mb, part, 0,      \
                          nullptr, addend, oph);                                                          \
-    else if (VST_BF_KSLICE && C % BK_ == 0)                                                         \
+    else if (C % BK_ == 0)                                                                          \
       hipLaunchKernelGGL((bf::conv_fprop_bf_k<T, true, 0>), grid, dim3(T::NT), 0, s, x, ws, wps, bias, y, \
                          H, W, C, Ho, Wo, Cop, S, st, padh, padw, reflect, act, slope, Mend, K, mb, part, 0,      \
                          nullptr, addend, oph);                                                          \
@@ -2297,120 +2082,63 @@ int bf_fprop_launch(const float* x, const void* wsplit, long wps, const float* b
   return check_launch("conv2d_fwd(bf16 split)");
 }
 
-
-// Border GEMM of the reflect-pad-1 data gradient (dgrad_border_pos rows): K-split count and slab
-// floats.  The rows (2(H+W)+8..+16 per image) are few, so the 256x128 (x6) / 128x128 (x3) tiles run
-// as ks K-range splits filling the CUs; the slabs are summed by dgrad_border_add_k.
-static void bf_border_plan(int N, int H, int W, int Cy, int Cx, int math, int* ks_out, long* mb_out) {
-  const int NB = bf::dgrad_border_rows(H, W);
-  const long Mb = (long)N * NB;
-  const int bm = math == VST_MATH_BF16X6 ? 256 : 128;
-  const long tiles = ((Mb + bm - 1) / bm) * ((Cx + 127) / 128);
-  const int nk = (9 * Cy + 31) / 32;
-  int ks = (int)(VST_NUM_CUS / (tiles > 0 ? tiles : 1));
-  ks = ks < 1 ? 1 : (ks > 16 ? 16 : ks);
-  while (ks > 1 && (ks - 1) * ((nk + ks - 1) / ks) >= nk) --ks;  // no empty split
-  *ks_out = ks;
-  *mb_out = Mb;
-}
-
-// The K-restricted border GEMM (REFL 5, 128x128 tiles): segment lengths and K-split count.  ks: at
-// least 4 K-steps per split and at most one CU round (g_border_ks overrides; g_border5 = false keeps the
-// full-K border rows of bf_border_plan).
-static constexpr bool g_border5 = true;
-static constexpr int g_border_ks = 0;
+// The K-restricted border GEMM (REFL 5, 128x128 tiles) of the reflect-pad-1 data gradient: segment
+// lengths and K-split count.  ks: at least 4 K-steps per split and at most one CU round.
 static void bf_border5_plan(int N, int H, int W, int Cy, int Cx, int* ks_out, int* lt, int* ll) {
   *lt = bf::border5_seg_rows(N, W + 2, 128);
   *ll = bf::border5_seg_rows(N, H, 128);
   const long tiles = (long)(2 * *lt + 2 * *ll) / 128 * ((Cx + 127) / 128);
   const int nk = (3 * Cy + 31) / 32;
-  int ks = g_border_ks > 0 ? g_border_ks : (int)(VST_NUM_CUS / (tiles > 0 ? tiles : 1));
-  if (g_border_ks <= 0 && ks > nk / 4) ks = nk / 4;
+  int ks = (int)(VST_NUM_CUS / (tiles > 0 ? tiles : 1));
+  if (ks > nk / 4) ks = nk / 4;
   ks = ks < 1 ? 1 : (ks > 16 ? 16 : ks);
   while (ks > 1 && (ks - 1) * ((nk + ks - 1) / ks) >= nk) --ks;  // no empty split
   *ks_out = ks;
 }
 
 bool bf_dgrad_refl1_ok(int N, int H, int W, int Cy, int Cx, int math) {
-  return math != VST_MATH_F32 && VST_BF_KSLICE && Cy % 32 == 0 && Cx % 4 == 0 && H >= 4 && W >= 4 && N > 0;
+  return math != VST_MATH_F32 && Cy % 32 == 0 && Cx % 4 == 0 && H >= 4 && W >= 4 && N > 0;
 }
 
-// where the border GEMM's slabs sit in the dgrad workspace (floats) and their split count / rows per image
-size_t bf_dgrad_refl1_slabs(int N, int H, int W, int Cy, int Cx, int math, BorderSlabs* b) {
-  if (g_border5) {
-    bf_border5_plan(N, H, W, Cy, Cx, &b->ks, &b->Lt, &b->Ll);
-    b->Mb = 2 * b->Lt + 2 * b->Ll;
-  } else {
-    long Mb;
-    bf_border_plan(N, H, W, Cy, Cx, math, &b->ks, &Mb);
-    b->Mb = (int)Mb;
-    b->Lt = bf::dgrad_border_rows(H, W);
-    b->Ll = 0;
-  }
-  return bf_fprop_ws_floats((long)N * H * W, Cx, Cy, 3, 3, math);
-}
-
+// the main conv's split-K workspace, then the border GEMM's ks5 slabs of 2 Lt + 2 Ll rows
 size_t bf_dgrad_refl1_ws_floats(int N, int H, int W, int Cy, int Cx, int math) {
-  int ks, ks5, lt, ll;
-  long Mb;
-  bf_border_plan(N, H, W, Cy, Cx, math, &ks, &Mb);
+  int ks5, lt, ll;
   bf_border5_plan(N, H, W, Cy, Cx, &ks5, &lt, &ll);
-  const size_t b4 = (size_t)ks * Mb * Cx, b5 = g_border5 ? (size_t)ks5 * (2 * lt + 2 * ll) * Cx : 0;
-  return bf_fprop_ws_floats((long)N * H * W, Cx, Cy, 3, 3, math) + (b4 > b5 ? b4 : b5);
+  return bf_fprop_ws_floats((long)N * H * W, Cx, Cy, 3, 3, math) + (size_t)ks5 * (2 * lt + 2 * ll) * Cx;
 }
 
 // dx = data gradient of ReflectionPad2d(1) + 3x3 conv (stride 1) from dy (+ addend), wsplit = the
 // VST_PACK_IKF planes of the conv weight: the interior as the zero-pad-1 forward conv (addend in its
-// epilogue), then the border GEMM (split-K slabs) and dgrad_border_add_k (add_border with VST_BORDER5
-// on: the K-restricted border GEMM and dgrad_border5_add_k).  Replaces the conv over the
-// (H+2) x (W+2) zero-padded frame + reflect fold.  add_border = false: the slabs (bf_dgrad_refl1_slabs)
-// are left for the caller (vst_conv2d_dgrad_refl_in adds them in its InstanceNorm-backward partial pass).
+// epilogue), then the K-restricted border GEMM (split-K slabs) and dgrad_border5_add_k.  Replaces the
+// conv over the (H+2) x (W+2) zero-padded frame + reflect fold.
 int bf_dgrad_refl1_launch(const float* dy, const void* wsplit, long wps, const float* addend, float* dx, int N, int H,
-                          int W, int Cy, int Cx, int math, hipStream_t s, float* ws, size_t ws_floats, bool add_border) {
-  int ks;
-  long Mb;
-  bf_border_plan(N, H, W, Cy, Cx, math, &ks, &Mb);
+                          int W, int Cy, int Cx, int math, hipStream_t s, float* ws, size_t ws_floats) {
+  VST_REQUIRE(ws_floats >= bf_dgrad_refl1_ws_floats(N, H, W, Cy, Cx, math), "dgrad_refl: workspace too small");
   const size_t main_ws = bf_fprop_ws_floats((long)N * H * W, Cx, Cy, 3, 3, math);
-  VST_REQUIRE(ws_floats >= main_ws + (size_t)ks * Mb * Cx, "dgrad_refl: workspace too small");
   if (int e = bf_fprop_launch(dy, wsplit, wps, nullptr, dx, N, H, W, Cy, H, W, Cx, 3, 3, 1, 1, 1, 0, VST_ACT_NONE, 0.f,
                               math, -1, s, nullptr, main_ws ? ws : nullptr, main_ws, addend))
     return e;
   float* slab = ws + main_ws;
   const __bf16* wb = reinterpret_cast<const __bf16*>(wsplit);
-  if (g_border5) {
-    int ks5, lt, ll;
-    bf_border5_plan(N, H, W, Cy, Cx, &ks5, &lt, &ll);
-    const int Mt = 2 * lt + 2 * ll, K = 3 * Cy;
-    VST_REQUIRE(ws_floats >= main_ws + (size_t)ks5 * Mt * Cx, "dgrad_refl: workspace too small");
-#define VST_B5(NP_)                                                                                            {                                                                                                             using T = bf::Tile<128, 128, 64, 32, 32, NP_>;                                                              const int nk = (K + T::BK - 1) / T::BK, spk = (nk + ks5 - 1) / ks5;                                         const dim3 grid(Mt / 128 * ceil_div(Cx, 128) * ks5);                                                        hipLaunchKernelGGL((bf::conv_fprop_bf_k<T, true, 5, true>), grid, dim3(T::NT), 0, s, dy, wb, wps, nullptr,                          dx, H, W, Cy, lt, ll, Cx, 3, N, 1, 1, 0, VST_ACT_NONE, 0.f, Mt, K, 0, nullptr, spk,                           slab, nullptr);                                                                        }
-    if (math == VST_MATH_BF16X6)
-      VST_B5(3)
-    else
-      VST_B5(2)
+  int ks5, lt, ll;
+  bf_border5_plan(N, H, W, Cy, Cx, &ks5, &lt, &ll);
+  const int Mt = 2 * lt + 2 * ll, K = 3 * Cy;
+#define VST_B5(NP_)                                                                                            \
+  {                                                                                                            \
+    using T = bf::Tile<128, 128, 64, 32, 32, NP_>;                                                             \
+    const int nk = (K + T::BK - 1) / T::BK, spk = (nk + ks5 - 1) / ks5;                                        \
+    const dim3 grid(Mt / 128 * ceil_div(Cx, 128) * ks5);                                                       \
+    hipLaunchKernelGGL((bf::conv_fprop_bf_k<T, true, 5, true>), grid, dim3(T::NT), 0, s, dy, wb, wps, nullptr, \
+                       dx, H, W, Cy, lt, ll, Cx, 3, N, 1, 1, 0, VST_ACT_NONE, 0.f, Mt, K, 0, nullptr, spk,     \
+                       slab, nullptr);                                                                         \
+  }
+  if (math == VST_MATH_BF16X6)
+    VST_B5(3)
+  else
+    VST_B5(2)
 #undef VST_B5
-    const int T = 2 * W + 2 * H;
-    if (add_border)
-      hipLaunchKernelGGL(bf::dgrad_border5_add_k, dim3(ceil_div((long)N * T, 16), ceil_div(Cx, 64)), dim3(256), 0, s,
-                       slab, ks5, Mt, Cx, dx, N, H, W, lt, ll);
-    return check_launch("conv2d_dgrad_refl");
-  }
-  const int NB = bf::dgrad_border_rows(H, W), K = 9 * Cy;
-  if (math == VST_MATH_BF16X6) {
-    using T = bf::Tile<256, 128, 64, 64, 32, 3>;
-    const int nk = (K + T::BK - 1) / T::BK, spk = (nk + ks - 1) / ks;
-    const dim3 grid(ceil_div(Mb, 256) * ceil_div(Cx, 128) * ks);
-    hipLaunchKernelGGL((bf::conv_fprop_bf_k<T, true, 4, true>), grid, dim3(T::NT), 0, s, dy, wb, wps, nullptr, dx, H,
-                       W, Cy, H, NB, Cx, 3, 1, 1, 1, 0, VST_ACT_NONE, 0.f, (int)Mb, K, 0, nullptr, spk, slab, nullptr);
-  } else {
-    using T = bf::Tile<128, 128, 64, 32, 32, 2>;
-    const int nk = (K + T::BK - 1) / T::BK, spk = (nk + ks - 1) / ks;
-    const dim3 grid(ceil_div(Mb, 128) * ceil_div(Cx, 128) * ks);
-    hipLaunchKernelGGL((bf::conv_fprop_bf_k<T, true, 4, true>), grid, dim3(T::NT), 0, s, dy, wb, wps, nullptr, dx, H,
-                       W, Cy, H, NB, Cx, 3, 1, 1, 1, 0, VST_ACT_NONE, 0.f, (int)Mb, K, 0, nullptr, spk, slab, nullptr);
-  }
-  if (add_border)
-    hipLaunchKernelGGL(bf::dgrad_border_add_k, dim3(ceil_div(Mb, 16), ceil_div(Cx, 64)), dim3(256), 0, s, slab, ks,
-                       (int)Mb, Cx, dx, H, W, NB);
+  hipLaunchKernelGGL(bf::dgrad_border5_add_k, dim3(ceil_div((long)N * (2 * W + 2 * H), 16), ceil_div(Cx, 64)),
+                     dim3(256), 0, s, slab, ks5, Mt, Cx, dx, N, H, W, lt, ll);
   return check_launch("conv2d_dgrad_refl");
 }
 
@@ -2422,7 +2150,7 @@ int bf_dgrad_refl1_launch(const float* dy, const void* wsplit, long wps, const f
 int bf_dgrad_refl1_inb_slices(int H, int W) { return H * W / 32 + (2 * W + 2 * H + 15) / 16; }
 
 bool bf_dgrad_refl1_inb_ok(int N, int H, int W, int Cy, int Cx, int math) {
-  if (math != VST_MATH_BF16X6 || !g_border5 || !bf_dgrad_refl1_ok(N, H, W, Cy, Cx, math) || (H * W) % 32) return false;
+  if (math != VST_MATH_BF16X6 || !bf_dgrad_refl1_ok(N, H, W, Cy, Cx, math) || (H * W) % 32) return false;
   int kd, m_split, tail_kind, m_first, fks;
   const long M = (long)N * H * W;
   if (M > (1L << 30)) return false;
@@ -2496,18 +2224,15 @@ int bf_dgrad_refl1_inb_launch(const float* dy, const void* wsplit, long wps, con
 // (ws[ph], ph = 2a + b: the phase packs' bf16 planes).  128x128 tiles (128x64 for Cop <= 64); C a
 // multiple of the K-slice (32).
 bool bf_convT_phases_ok(int C, int Cop, int math) {
-  return math != VST_MATH_F32 && VST_BF_KSLICE && C % 32 == 0 && Cop % 4 == 0;
+  return math != VST_MATH_F32 && C % 32 == 0 && Cop % 4 == 0;
 }
 
-// The phase tile (x6): Cop > 64 on 256x128 (8 waves of 64x64) unless its grid's rounds cost more than the
-// 128x128 tile's (the N = 4 PatchGAN data gradients: 68 blocks, 77 us vs 51 us), Cop <= 64 on 64x64 (4 waves of
-// 32x32).  Round 5
-// sweep (profiles/r05e_convT_wgrad_tiles.jsonl, same box): the 256 -> 128 ConvTranspose / stride-2 data
+// The phase tile.  x3: 128x128 (8 waves of 64x32), 128x64 for Cop <= 64.  x6: Cop > 64 on 256x128 (8 waves of
+// 64x64) unless its grid's rounds cost more than the 8-wave 128x128 tile's (the N = 4 PatchGAN data gradients: 68
+// blocks, 77 us vs 51 us), Cop <= 64 on 64x64 (4 waves of 32x32).  Round 5 sweep
+// (profiles/r05e_convT_wgrad_tiles.jsonl, same box): the 256 -> 128 ConvTranspose / stride-2 data
 // gradient 144 -> 124 us at N = 8 (188 -> 167 at N = 12) against 128x128 tiles of 8 x (64x32) waves; the
-// 128 -> 64 one 150 -> 145 us against 128x64.  g_convt_tile (developer A/B): 0 = the round-4 tiles
-// (128x128 8 waves / 128x64 4 waves), 1 = 256x128 / 128x64, 2 = 128x128 4 waves / 64x64; -1 = the default.
-static constexpr int g_convt_tile = -1;
-
+// 128 -> 64 one 150 -> 145 us against 128x64.
 int bf_convT_phases_launch(const float* x, const void* const ws[4], const float* bias, float* y, int N, int H, int W,
                            int C, int Cop, int act, float slope, int math, hipStream_t s, int full) {
   VST_REQUIRE(bf_convT_phases_ok(C, Cop, math), "convT phases: unsupported shape / arithmetic");
@@ -2528,41 +2253,31 @@ int bf_convT_phases_launch(const float* x, const void* const ws[4], const float*
     if (jb) jb->t0[4] = tt;
     return tt;
   };
-  int tk = math != VST_MATH_BF16X6 ? 0 : (g_convt_tile >= 0 ? g_convt_tile : (bn == 128 ? 1 : 2));
-  if (math == VST_MATH_BF16X6 && g_convt_tile < 0 && bn == 128) {
+  const bool x6 = math == VST_MATH_BF16X6;
+  bool big = false;  // x6, Cop > 64: 256x128 tiles
+  if (x6 && bn == 128) {
     // 256x128 only where its rounds cost less than the 8-wave 128x128 tile's (one block per CU either way;
     // a 32-deep K-step ~2.25 vs ~1.5 us): the small grids (the PatchGAN k4s2 data gradients at N = 4, 68
     // blocks of 256x128) keep 128x128
     const long r256 = (grid_of(256, nullptr) + VST_NUM_CUS - 1) / VST_NUM_CUS;
     const long r128 = (grid_of(128, nullptr) + VST_NUM_CUS - 1) / VST_NUM_CUS;
-    tk = r256 * 2.25 <= r128 * 1.5 ? 1 : 0;
+    big = r256 * 2.25 <= r128 * 1.5;
   }
-  const int bm = (tk == 1 && bn == 128) ? 256 : ((tk == 2 && bn == 64) ? 64 : 128);
+  const int bm = big ? 256 : ((x6 && bn == 64) ? 64 : 128);
   bf::PhaseJobs jobs;
   const int t = grid_of(bm, &jobs);
-#define VST_CTB(BM_, BN_, WM_, WN_)                                                                       \
+#define VST_CT(BM_, BN_, WM_, WN_, NP_)                                                                   \
   {                                                                                                        \
-    using T = bf::Tile<BM_, BN_, WM_, WN_, 32, 3>;                                                         \
+    using T = bf::Tile<BM_, BN_, WM_, WN_, 32, NP_>;                                                       \
     hipLaunchKernelGGL(bf::conv_convT_phases_k<T>, dim3(t), dim3(T::NT), 0, s, x, jobs, bias, y, N, H, W, C, Cop, \
                        act, slope, full);                                                                  \
   }
-#define VST_CT(BN_, WN_, NP_)                                                                             \
-  {                                                                                                        \
-    using T = bf::Tile<128, BN_, 64, WN_, 32, NP_>;                                                        \
-    hipLaunchKernelGGL(bf::conv_convT_phases_k<T>, dim3(t), dim3(T::NT), 0, s, x, jobs, bias, y, N, H, W, C, Cop, \
-                       act, slope, full);                                                                  \
-  }
-  if (math == VST_MATH_BF16X6 && tk == 1) {
-    if (bn == 64) VST_CT(64, 32, 3) else VST_CTB(256, 128, 64, 64)
-  } else if (math == VST_MATH_BF16X6 && tk == 2) {
-    if (bn == 64) VST_CTB(64, 64, 32, 32) else VST_CTB(128, 128, 64, 64)
-  } else if (math == VST_MATH_BF16X6) {
-    if (bn == 64) VST_CT(64, 32, 3) else VST_CT(128, 32, 3)
+  if (x6) {
+    if (bn == 64) VST_CT(64, 64, 32, 32, 3) else if (big) VST_CT(256, 128, 64, 64, 3) else VST_CT(128, 128, 64, 32, 3)
   } else {
-    if (bn == 64) VST_CT(64, 32, 2) else VST_CT(128, 32, 2)
+    if (bn == 64) VST_CT(128, 64, 64, 32, 2) else VST_CT(128, 128, 64, 32, 2)
   }
 #undef VST_CT
-#undef VST_CTB
   return check_launch("conv2d_convT_s2");
 }
 
@@ -2602,7 +2317,7 @@ void bf_wgrad_launch(const float* xt, const void* dyp, float* slab, int N, int H
 }
 
 bool bf_wgrad_nhwc_ok(int kind, int Wo, int Cx, int Cyp) {
-  return VST_BF_MF16 && (kind == 7 || kind == 0) && Wo % 32 == 0 && Cx % 8 == 0 && Cyp % 8 == 0;
+  return (kind == 7 || kind == 0) && Wo % 32 == 0 && Cx % 8 == 0 && Cyp % 8 == 0;
 }
 
 // kind 7: 256x128 tiles (8 waves of 64x64); kind 0: 128x128 (8 waves of 64x32).  bf32: dy fp32 NHWC (pps unused)
@@ -2637,18 +2352,7 @@ void bf_wgrad_geom(int kind, int math, int* bm, int* bn, int* bk, int* slots) {
 using namespace vst;
 
 extern "C" const char* vst_build_info(void) {
-#define VST_STR2(x) #x
-#define VST_STR(x) VST_STR2(x)
-#if VST_BF_MF16
-#define VST_X6_MFMA "16x16x32"
-#else
-#define VST_X6_MFMA "32x32x16"
-#endif
-  return "x6_mfma=" VST_X6_MFMA " x3_mfma=32x32x16 kslice=" VST_STR(VST_BF_KSLICE) " x6_256=" VST_STR(VST_BF_X6_256)
-         " m16_store=" VST_STR(VST_M16_STORE) " m16_sched=" VST_STR(VST_M16_SCHED);
-#undef VST_X6_MFMA
-#undef VST_STR
-#undef VST_STR2
+  return "x6_mfma=16x16x32 x3_mfma=32x32x16";
 }
 
 extern "C" int vst_weight_split(const float* w, void* out, long n, void* stream) {
@@ -2671,5 +2375,5 @@ extern "C" int vst_conv2d_dgrad_refl(const float* dy, const void* wsplit, const 
     return VST_EUNSUPPORTED;
   }
   return bf_dgrad_refl1_launch(dy, wsplit, (long)Cx * 9 * Cy, addend, dx, N, H, W, Cy, Cx, math, (hipStream_t)stream,
-                               ws, ws_bytes / sizeof(float), true);
+                               ws, ws_bytes / sizeof(float));
 }

@@ -64,9 +64,6 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
 
-#ifndef VST_C4_GRP
-#define VST_C4_GRP 0  // ring kernel wave groups: 0 = waves {0-3} / {4-7}, 1 = even / odd waves
-#endif
 // one output-row segment: image n, output row ho, columns [wo0, wo0 + L)
 struct Seg {
   int n, ho, wo0, L;
@@ -466,9 +463,9 @@ __global__ __launch_bounds__(NT, 1) void conv_c4_ring_k(const float* __restrict_
   }
   const int kq = lane >> 4;
   const int sub = wave;      // this wave's 32-pixel sub-tile of every segment
-  // one wave of each group per SIMD; an SGPR value, so `grp` branches are scalar (two exclusive paths,
+  // wave groups {0-3} / {4-7}: one wave of each group per SIMD; an SGPR value, so `grp` branches are scalar (two exclusive paths,
   // each with its own counted waits) rather than exec-masked sequences of both
-  const int grp = __builtin_amdgcn_readfirstlane(VST_C4_GRP ? (wave & 1) : (wave >> 2));
+  const int grp = __builtin_amdgcn_readfirstlane(wave >> 2);
   const int HWo = Ho * Wo;
   f32x4v acc[2][4];
 

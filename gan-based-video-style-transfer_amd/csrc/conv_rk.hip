@@ -30,9 +30,7 @@ constexpr int NOPOS = -(1 << 20);
 #ifndef VST_RK_PROBE
 #define VST_RK_PROBE 0  // developer probes: 1 = fprop without global loads, 2 = without MFMAs
 #endif
-#ifndef VST_RK_LG
-#define VST_RK_LG 4   // the next stage's global loads are spread over the first LG MFMA groups
-#endif
+constexpr int RK_LG = 4;  // the next stage's global loads are spread over the first LG MFMA groups
 
 template <int BM, int BN, int WM, int WN, int BK_, int MATH_ = VST_MATH_F32>
 struct Tile {
@@ -242,7 +240,7 @@ __device__ __forceinline__ void main_loop(float* smem, int nk, f32x16 (&acc)[T::
                                           LoadOne load_one, Adv adv, Store store) {
   constexpr int BK = T::BK;
   constexpr int NG = T::X3 ? BK / 16 : BK / 8;  // k groups per stage (hook slots)
-  constexpr int LG = VST_RK_LG < NG ? VST_RK_LG : NG;
+  constexpr int LG = RK_LG < NG ? RK_LG : NG;
   constexpr int PER = (NLOAD + LG - 1) / LG;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm0 = (wave / T::WAVES_N) * T::WM_, wn0 = (wave % T::WAVES_N) * T::WN_;

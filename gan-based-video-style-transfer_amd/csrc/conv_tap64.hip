@@ -251,9 +251,6 @@ static constexpr bool g_tap64 = true;
 // instead of one whole row per group — a row's K-steps each split a new input row for only one output row
 // (RI = 1), 4x the operand-split VALU per MFMA of the 4-row groups (the C3 / Sintel-size last layer and the
 // first layer's data gradient ran ~3.5x slower per pixel than at 256 wide).
-#ifndef VST_TAP64_SEG
-#define VST_TAP64_SEG 1
-#endif
 
 // Does the direct kernel take this tap conv?  64 input channels, 7 x 7, 4 (padded) outputs, x6 / x3
 // math, W in {256, 512, 1024} (a group is 1024 / W whole rows, or 4 rows of a 1024-wide row's column segment),
@@ -269,7 +266,7 @@ int tap64_launch(const float* x, const void* wsplit, long wps, const float* bias
   VST_REQUIRE(Ho > 0 && Wo > 0 && (!reflect || (pad < H && pad < W)), "tap64: bad padding");
   VST_REQUIRE(W % 256 == 0 && tap64::GQ % W == 0, "tap64: W must be 256, 512 or 1024");
   VST_REQUIRE((long)N * H * W * tap64::CI * 4 < 0x7ffffff0L, "tap64: input over 2 GB (32-bit buffer offsets)");
-  const bool seg = VST_TAP64_SEG && W == 1024;
+  const bool seg = W == 1024;
   const int RI = seg ? 4 : tap64::GQ / W, gpi = (Ho + RI - 1) / RI;
   const int outw = seg ? tap64::GQ / 4 - (tap64::R - 1) : Wo, nseg = seg ? (Wo + outw - 1) / outw : 1;
   const int groups = N * gpi * nseg;
