@@ -226,6 +226,14 @@ SIGNATURES = {
     "vst_l1_mean_bwd": (I, [P, P, P, P, L, I, I, F, P]),
     "vst_mse_const_fwd": (I, [P, F, P, P, L, I, I, F, P]),
     "vst_mse_const_bwd": (I, [P, F, P, P, L, I, I, F, P]),
+    "vst_loss_r1": (I, [P, P, P, I, L, P]),
+    "vst_loss_r1_bwd": (I, [P, P, P, I, L, P]),
+    "vst_loss_bce_logits": (I, [P, P, P, I, I, I, F, P]),
+    "vst_loss_bce_logits_bwd": (I, [P, P, P, P, I, I, I, F, P]),
+    "vst_r1_fwd": (I, [P, P, P, I, I, I, P]),
+    "vst_r1_bwd": (I, [P, P, P, I, I, I, P]),
+    "vst_bce_logits_fwd": (I, [P, P, P, I, I, I, F, P]),
+    "vst_bce_logits_bwd": (I, [P, P, P, P, I, I, I, F, P]),
 }
 
 

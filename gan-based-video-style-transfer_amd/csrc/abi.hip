@@ -1,9 +1,9 @@
 // The SURVEY §8b spelling of the C ABI: a conv descriptor (vst_conv_desc), one workspace query
 // (vst_workspace_size) and the entry-point names a binder written from that contract expects
 // (vst_conv2d_{fwd,dgrad,wgrad}_desc, vst_adam_multi_tensor, vst_gram, vst_corr_volume,
-// vst_warp_bilinear_*, vst_masked_sqdiff_mean_*, vst_l1_mean_*, vst_mse_const_*).  Each is a host-side
-// wrapper that validates the descriptor and forwards to the kernels behind the shape-argument entry
-// points (conv.hip, loss.hip, flow.hip, style.hip, misc.hip); no kernel lives here.
+// vst_warp_bilinear_*, vst_masked_sqdiff_mean_*, vst_l1_mean_*, vst_mse_const_*, vst_r1_*, vst_bce_logits_*).
+// Each is a host-side wrapper that validates the descriptor and forwards to the kernels behind the
+// shape-argument entry points (conv.hip, loss.hip, r1.hip, flow.hip, style.hip, misc.hip); no kernel lives here.
 #include "common.h"
 
 namespace {
@@ -215,4 +215,24 @@ extern "C" int vst_mse_const_fwd(const float* a, float target, float* loss, floa
 extern "C" int vst_mse_const_bwd(const float* a, float target, const float* gout, float* grad, long npix, int Cs,
                                  int Cl, float scale, void* stream) {
   return vst_loss_mse_const_bwd(a, target, gout, grad, npix, Cs, Cl, scale, stream);
+}
+
+extern "C" int vst_r1_fwd(const float* g, float* loss, double* part, int B, int H, int W, void* stream) {
+  VST_REQUIRE(H > 0 && W > 0, "r1_fwd: bad image size");
+  return vst_loss_r1(g, loss, part, B, (long)H * W, stream);
+}
+
+extern "C" int vst_r1_bwd(const float* g, const float* gout, float* u, int B, int H, int W, void* stream) {
+  VST_REQUIRE(H > 0 && W > 0, "r1_bwd: bad image size");
+  return vst_loss_r1_bwd(g, gout, u, B, (long)H * W, stream);
+}
+
+extern "C" int vst_bce_logits_fwd(const float* z, const long* y, float* loss, int B, int D, int nd, float target,
+                                  void* stream) {
+  return vst_loss_bce_logits(z, y, loss, B, D, nd, target, stream);
+}
+
+extern "C" int vst_bce_logits_bwd(const float* z, const long* y, const float* gout, float* grad, int B, int D, int nd,
+                                  float target, void* stream) {
+  return vst_loss_bce_logits_bwd(z, y, gout, grad, B, D, nd, target, stream);
 }

@@ -20,6 +20,9 @@ library's NHWC layout on the device.  Backward passes are themselves ``vst::`` o
         (the fc itself, like every nn.Linear of these nets, is vst::conv2d over [B, K, 1, 1])
   vst::avg_pool2(x)                            F.avg_pool2d(x, 2), core/model.py:45-55
   vst::merge(a, b, mode, scale)                core/model.py:62-64, :116-120: (a + f(b)) * scale, f = identity | pool | up
+  vst::r1_penalty(grad)                        core/solver.py:473-475, the R1 penalty of an image gradient; its backward
+        op is differentiable too, so create_graph runs through it
+  vst::bce_logits(logits, y, target)           core/solver.py:459-463 adv_loss of logits[arange(B), y], y a device int64 [B]
   vst::warp_bilinear(x, flow)                  utils/flowtools.py:18-32 (F.grid_sample, zeros)
   vst::fbcheck(flow_fw, flow_bw)               utils/flowtools.py:34-58 (fbcCheckTorch)
   vst::temporal_loss(a, b, flow, mask, lam)    CycleGANCon cycle_gan_model.py:191-204
@@ -504,6 +507,107 @@ def _merge_bwd(ctx, grad):
 merge.register_autograd(_merge_bwd, setup_context=_merge_setup)
 
 
+# ------------------------------------------------------------------- r1_penalty / bce_logits
+def _img_grad(g, what):
+    ops._dev_check(g)
+    if g.dim() != 4 or g.shape[1] > 3:
+        raise ValueError("vst::%s: an image gradient [B, C <= 3, H, W], got %s" % (what, tuple(g.shape)))
+
+
+@torch.library.custom_op("vst::r1_penalty", mutates_args=())
+def r1_penalty(grad: Tensor) -> Tensor:
+    """0.5 * grad.pow(2).view(B, -1).sum(1).mean(0) of the image gradient [B, 3, H, W] (core/solver.py:473-475)."""
+    _img_grad(grad, "r1_penalty")
+    return ops.r1(ops.nchw_to_nhwc(grad.contiguous(), 4))
+
+
+@r1_penalty.register_fake
+def _(grad):
+    return grad.new_empty(())
+
+
+@torch.library.custom_op("vst::r1_penalty_backward", mutates_args=())
+def r1_penalty_backward(gout: Tensor, grad: Tensor) -> Tensor:
+    """gout * grad / B: the gradient of vst::r1_penalty, linear in grad."""
+    _img_grad(grad, "r1_penalty_backward")
+    return ops.nhwc_to_nchw(ops.r1_bwd(ops.nchw_to_nhwc(grad.contiguous(), 4), gout.contiguous()), grad.shape[1])
+
+
+@r1_penalty_backward.register_fake
+def _(gout, grad):
+    return torch.empty_like(grad)
+
+
+def _r1_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+
+
+def _r1_bwd(ctx, gout):
+    return torch.ops.vst.r1_penalty_backward(gout, ctx.saved_tensors[0])
+
+
+def _r1b_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _r1b_bwd(ctx, ggu):
+    """The double backward: d/d grad is the same kernel applied to ggu; d/d gout = <ggu, grad> / B."""
+    gout, grad = ctx.saved_tensors
+    d_gout = (ggu * grad).sum() / grad.shape[0] if ctx.needs_input_grad[0] else None
+    d_grad = torch.ops.vst.r1_penalty_backward(gout, ggu.contiguous()) if ctx.needs_input_grad[1] else None
+    return d_gout, d_grad
+
+
+r1_penalty.register_autograd(_r1_bwd, setup_context=_r1_setup)
+r1_penalty_backward.register_autograd(_r1b_bwd, setup_context=_r1b_setup)
+
+
+def _padded_logits(logits, y, what):
+    ops._dev_check(logits)
+    if logits.dim() != 2 or y.dim() != 1 or y.shape[0] != logits.shape[0]:
+        raise ValueError("vst::%s: logits [B, num_domains] and y [B], got %s and %s"
+                         % (what, tuple(logits.shape), tuple(y.shape)))
+    z = logits.new_zeros((logits.shape[0], ops.cpad(logits.shape[1])))
+    z[:, :logits.shape[1]] = logits
+    return z, y.long().contiguous()
+
+
+@torch.library.custom_op("vst::bce_logits", mutates_args=())
+def bce_logits(logits: Tensor, y: Tensor, target: float) -> Tensor:
+    """adv_loss(logits[arange(B), y], target) (core/solver.py:459-463), target 0 or 1."""
+    z, yl = _padded_logits(logits, y, "bce_logits")
+    return ops.bce_logits(z, yl, logits.shape[1], target)
+
+
+@bce_logits.register_fake
+def _(logits, y, target):
+    return logits.new_empty(())
+
+
+@torch.library.custom_op("vst::bce_logits_backward", mutates_args=())
+def bce_logits_backward(gout: Tensor, logits: Tensor, y: Tensor, target: float) -> Tensor:
+    z, yl = _padded_logits(logits, y, "bce_logits_backward")
+    return ops.bce_logits_bwd(z, yl, logits.shape[1], target, gout.contiguous())[:, :logits.shape[1]].contiguous()
+
+
+@bce_logits_backward.register_fake
+def _(gout, logits, y, target):
+    return torch.empty_like(logits)
+
+
+def _bce_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+    ctx.target = inputs[2]
+
+
+def _bce_bwd(ctx, gout):
+    logits, y = ctx.saved_tensors
+    return torch.ops.vst.bce_logits_backward(gout, logits, y, ctx.target), None, None
+
+
+bce_logits.register_autograd(_bce_bwd, setup_context=_bce_setup)
+
+
 # ------------------------------------------------------------------------------------ flow
 @torch.library.custom_op("vst::warp_bilinear", mutates_args=())
 def warp_bilinear(x: Tensor, flow: Tensor) -> Tensor:
@@ -798,4 +902,5 @@ OPS: List[str] = ["conv2d", "conv2d_backward", "conv_transpose2d", "conv_transpo
                   "resize_bilinear", "gram", "gram_backward", "adam_", "ruder_stack", "ruder_stack_backward",
                   "ruder_temporal", "ruder_temporal_backward", "cond_instance_norm", "cond_instance_norm_backward",
                   "instance_norm_skip", "instance_norm_skip_backward", "adain_act", "adain_act_backward",
-                  "avg_pool2", "avg_pool2_backward", "merge", "merge_backward"]
+                  "avg_pool2", "avg_pool2_backward", "merge", "merge_backward", "r1_penalty", "r1_penalty_backward",
+                  "bce_logits", "bce_logits_backward"]

@@ -832,6 +832,68 @@ def loss_mse_const_bwd(a, target, gout, scale=1.0, cl=1):
     return g
 
 
+R1_PART_DOUBLES = 1024  # VST_R1_PART_DOUBLES
+
+
+def _r1_check(what, g):
+    _dev_check(g)
+    if g.dim() != 4 or g.shape[-1] != 4:
+        raise ValueError("%s: the image gradient is NHWC [B, H, W, 4], got %s" % (what, tuple(g.shape)))
+
+
+def r1(g):
+    """r1_reg of the NHWC-4 image gradient g: 0.5 / B * sum over h, w and the three real lanes of g^2
+    (vst_loss_r1; fp64 accumulation in a fixed order)."""
+    _r1_check("r1", g)
+    B, H, W, _ = g.shape
+    loss = torch.empty((), device=g.device)
+    part = torch.empty(R1_PART_DOUBLES, dtype=torch.float64, device=g.device)
+    _call("vst_loss_r1", _p(g), _p(loss), _p(part), B, H * W, _stream())
+    return loss
+
+
+def r1_bwd(g, gout):
+    """gout * g / B with lane 3 zeroed (vst_loss_r1_bwd); gout a device scalar."""
+    _r1_check("r1_bwd", g)
+    _dev_check(gout)
+    if gout.numel() != 1:
+        raise ValueError("r1_bwd: gout is a scalar, got %s" % (tuple(gout.shape),))
+    B, H, W, _ = g.shape
+    u = torch.empty_like(g)
+    _call("vst_loss_r1_bwd", _p(g), _p(gout), _p(u), B, H * W, _stream())
+    return u
+
+
+def _bce_check(what, z, y, nd, target):
+    _dev_check(z)
+    if z.dim() != 2 or z.shape[1] % 4 or not 0 < nd <= z.shape[1]:
+        raise ValueError("%s: logits are [B, cpad(num_domains)] with %d domains, got %s" % (what, nd, tuple(z.shape)))
+    if not y.is_cuda or y.dtype != torch.int64 or not y.is_contiguous() or tuple(y.shape) != (z.shape[0],):
+        raise ValueError("%s: domain ids are a contiguous int64 device tensor [%d]" % (what, z.shape[0]))
+    if target not in (0, 1):
+        raise ValueError("%s: target must be 0 or 1, got %r" % (what, target))
+
+
+def bce_logits(z, y, nd, target):
+    """mean_b softplus(-+z[b, y[b]]): binary_cross_entropy_with_logits of the selected domain's logit against the
+    constant target (vst_loss_bce_logits)."""
+    _bce_check("bce_logits", z, y, nd, target)
+    loss = torch.empty((), device=z.device)
+    _call("vst_loss_bce_logits", _p(z), _p(y), _p(loss), z.shape[0], z.shape[1], int(nd), float(target), _stream())
+    return loss
+
+
+def bce_logits_bwd(z, y, nd, target, gout):
+    """The dense [B, D] gradient of bce_logits: (sigmoid(z) - target) / B * gout in column y[b], zeros elsewhere
+    (vst_loss_bce_logits_bwd)."""
+    _bce_check("bce_logits_bwd", z, y, nd, target)
+    _dev_check(gout)
+    grad = torch.empty_like(z)
+    _call("vst_loss_bce_logits_bwd", _p(z), _p(y), _p(gout), _p(grad), z.shape[0], z.shape[1], int(nd), float(target),
+          _stream())
+    return grad
+
+
 # -------------------------------------------------------------------------------- optimizer
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step):
     _dev_check(p, g, m, v)

@@ -15,7 +15,13 @@ image / logit ends):
 The learned shortcut's 1x1 conv runs on the low-resolution side of its resampling (ResBlk: pool, then conv;
 AdainResBlk: conv, then upsample in the merge), a quarter of the reference order's work; see DESIGN.md.
 
-Left to the training pull request: the solver's losses, the R1 penalty (a double backward) and the EMA loop.
+The discriminator half of the solver (core/solver.py:167-176, :360-382, :459-476) is here too: ``adv_loss``, ``r1_reg``,
+``compute_d_loss`` / ``d_losses``, ``he_init`` and ``DiscriminatorTrainer`` (torch.optim.Adam with the reference's
+weight decay, ``d_step``).  The R1 penalty differentiates ||dD/dx_real||^2 with respect to D's weights, so every node
+under the discriminator is differentiable twice (see the note above ``_INPUT_GRAD_ONLY``); the penalty itself and the
+adversarial term (BCE with logits fused with the domain gather) are the kernels vst_loss_r1 / vst_loss_bce_logits.
+
+Still missing: ``compute_g_loss`` (the generator half of the step) and the EMA train loop around both halves.
 ``w_hpf > 0`` (HighPass / FAN) and ``masks`` are not on the HIP path and raise NotImplementedError.
 """
 import copy
@@ -24,6 +30,7 @@ import os
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from .faststyle import InstanceNormAffine
@@ -53,8 +60,86 @@ def _packs(mod):
     return ent[1]
 
 
+# The nodes under the discriminator (conv, LeakyReLU, pooling, merge, the layout conversions) are differentiable
+# twice: each backward is itself made of autograd Functions over the same kernels, so the R1 penalty's
+# autograd.grad(create_graph=True) leaves a graph that loss.backward() walks down to D's weights.  A conv's three
+# bilinear kernels are each other's derivatives (forward <-> data gradient, both -> weight gradient); the activation
+# mask, the pooling backward and the merge backward are linear maps whose adjoints are kernels the forward already has.
+# The norm and upsampling nodes (generator only) stay first-order and say so (once_differentiable).
+#
+# Set by _input_grad around the penalty's autograd.grad (a module global: the engine runs the backward on its device
+# thread): that sweep asks for the image gradient alone, and the weight / bias gradients are no part of its graph.
+_INPUT_GRAD_ONLY = [False]
+
+
+class _MaskFn(torch.autograd.Function):
+    """g * act'(y) through the activation's output y: linear in g and its own adjoint; d/dy = 0 almost everywhere."""
+
+    @staticmethod
+    def forward(ctx, g, y, act):
+        ctx.save_for_backward(y)
+        ctx.act = act
+        return ops.act_bwd(g, y, act, SLOPE)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg):
+        (y,) = ctx.saved_tensors
+        return ops.act_bwd(gg.contiguous(), y, ctx.act, SLOPE), None, None
+
+
+def _wgrad(x, gz, weight, has_bias, k, stride, pad):
+    """(dw, db) of a conv from its input and its output's gradient: one vst_conv2d_wgrad launch."""
+    co, ci = weight.shape[0], weight.shape[1]
+    dw = torch.zeros_like(weight)
+    db = torch.zeros(co, device=x.device) if has_bias else None
+    ops.conv2d_wgrad(x, gz, dw, db, k, k, stride, pad, "zero", co, ci, ci * k * k, k * k, accumulate=False)
+    return dw, db
+
+
+class _DgradFn(torch.autograd.Function):
+    """dx = conv^T(gz; W), bilinear in (gz, W): its backward is the forward conv of ggx (for gz) and the weight
+    gradient of (ggx, gz) (for W)."""
+
+    @staticmethod
+    def forward(ctx, gz, weight, mod, ck, k, stride, pad, xshape):
+        ctx.save_for_backward(gz)
+        ctx.conf = (weight, mod, k, stride, pad)
+        _, H, W, C = xshape
+        return ops.conv2d_tfwd(gz, ck, None, H, W, C, k, k, stride, pad)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ggx):
+        (gz,) = ctx.saved_tensors
+        weight, mod, k, stride, pad = ctx.conf
+        ggx = ggx.contiguous()
+        d_gz = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_gz = ops.conv2d_fwd(ggx, _packs(mod)[0], None, cpad(weight.shape[0]), k, k, stride, pad, "zero",
+                                  role="bwd")
+        if ctx.needs_input_grad[1]:
+            d_w, _ = _wgrad(ggx, gz, weight, False, k, stride, pad)
+        return d_gz, d_w, None, None, None, None, None, None
+
+
+class _WgradFn(torch.autograd.Function):
+    """(dw, db) of a conv.  First-order: the R1 penalty never differentiates it (its sweep computes no weight
+    gradient, and the masks have zero derivative), and anything that tries is refused."""
+
+    @staticmethod
+    def forward(ctx, x, gz, weight, has_bias, k, stride, pad):
+        return _wgrad(x, gz, weight, has_bias, k, stride, pad)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ggw, ggb):
+        raise RuntimeError("the weight gradient of a StarGAN v2 conv is first-order only")
+
+
 class _ConvFn(torch.autograd.Function):
-    """act(conv(x, weight) + bias), zero padding; weight [Co, Ci, k, k] or a Linear's [Co, Ci] (k = 1)."""
+    """act(conv(x, weight) + bias), zero padding; weight [Co, Ci, k, k] or a Linear's [Co, Ci] (k = 1).
+    backward: activation mask -> data gradient -> weight and bias gradient, each a Function."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod, k, stride, pad, act):
@@ -62,25 +147,21 @@ class _ConvFn(torch.autograd.Function):
         role = "fwd" if any(ctx.needs_input_grad[:3]) else "infer"
         y = ops.conv2d_fwd(x, kc, bp, cpad(weight.shape[0]), k, k, stride, pad, "zero", act=act, slope=SLOPE, role=role)
         ctx.save_for_backward(x, y if act != "none" else None)
-        ctx.conf = (weight, bias is not None, ck, k, stride, pad, act)
+        ctx.conf = (weight, bias is not None, mod, ck, k, stride, pad, act)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, y = ctx.saved_tensors
-        weight, has_bias, ck, k, stride, pad, act = ctx.conf
-        gy = gy.contiguous()
+        weight, has_bias, mod, ck, k, stride, pad, act = ctx.conf
+        gz = gy.contiguous()
         if act != "none":
-            gy = ops.act_bwd(gy, y, act, SLOPE)
-        co, ci = weight.shape[0], weight.shape[1]
+            gz = _MaskFn.apply(gz, y, act)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            N, H, W, C = x.shape
-            dx = ops.conv2d_tfwd(gy, ck, None, H, W, C, k, k, stride, pad)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            dw = torch.zeros_like(weight)
-            db = torch.zeros(co, device=x.device) if has_bias else None
-            ops.conv2d_wgrad(x, gy, dw, db, k, k, stride, pad, "zero", co, ci, ci * k * k, k * k, accumulate=False)
+            dx = _DgradFn.apply(gz, weight, mod, ck, k, stride, pad, x.shape)
+        if not _INPUT_GRAD_ONLY[0] and (ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])):
+            dw, db = _WgradFn.apply(x, gz, weight.detach(), has_bias, k, stride, pad)
         return dx, dw, db, None, None, None, None, None
 
 
@@ -107,6 +188,7 @@ class _AffineNormActFn(torch.autograd.Function):
         return ops.instnorm_affine_fwd(x, st, gamma.detach(), beta.detach(), "lrelu", slope=SLOPE)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         x, st, gamma, beta = ctx.saved_tensors
         dg, db = torch.empty_like(gamma), torch.empty_like(beta)
@@ -125,6 +207,7 @@ class _AdaINActFn(torch.autograd.Function):
         return ops.adain_fwd(x, st, h, "lrelu", SLOPE)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         x, st, h = ctx.saved_tensors
         dh = torch.empty_like(h) if ctx.needs_input_grad[1] else None
@@ -142,7 +225,7 @@ class _LReluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (y,) = ctx.saved_tensors
-        return ops.act_bwd(g.contiguous(), y, "lrelu", SLOPE)
+        return _MaskFn.apply(g.contiguous(), y, "lrelu")
 
 
 class _PoolFn(torch.autograd.Function):
@@ -152,7 +235,20 @@ class _PoolFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return ops.avgpool2_bwd(g.contiguous())
+        return _PoolBwdFn.apply(g.contiguous())
+
+
+class _PoolBwdFn(torch.autograd.Function):
+    """g / 4 spread over each 2x2 window; its adjoint is the pooling itself."""
+
+    @staticmethod
+    def forward(ctx, g):
+        return ops.avgpool2_bwd(g)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gg):
+        return ops.avgpool2(gg.contiguous())
 
 
 class _Up2Fn(torch.autograd.Function):
@@ -161,6 +257,7 @@ class _Up2Fn(torch.autograd.Function):
         return ops.upsample2x(x)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         return ops.upsample2x_bwd(g.contiguous())
 
@@ -175,8 +272,100 @@ class _MergeFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        ga, gb = ops.merge_bwd(g.contiguous(), ctx.mode, RSQRT2)
+        ga, gb = _MergeBwdFn.apply(g.contiguous(), ctx.mode)
         return ga, gb, None
+
+
+class _MergeBwdFn(torch.autograd.Function):
+    """g -> (g, f^T(g)) / sqrt(2); its adjoint (gga, ggb) -> (gga + f(ggb)) / sqrt(2) is the merge itself."""
+
+    @staticmethod
+    def forward(ctx, g, mode):
+        ctx.mode = mode
+        return ops.merge_bwd(g, mode, RSQRT2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gga, ggb):
+        return ops.merge(gga.contiguous(), ggb.contiguous(), ctx.mode, RSQRT2), None
+
+
+class _ToNHWC2(torch.autograd.Function):
+    """NCHW -> NHWC with channel stride cs; the pair below is each other's backward, so an image gradient taken
+    through it can be differentiated again."""
+
+    @staticmethod
+    def forward(ctx, x, cs):
+        ctx.c = x.shape[1]
+        return ops.nchw_to_nhwc(x.contiguous(), cs)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _ToNCHW2.apply(g.contiguous(), ctx.c), None
+
+
+class _ToNCHW2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, c):
+        ctx.cs = y.shape[-1]
+        return ops.nhwc_to_nchw(y.contiguous(), c)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _ToNHWC2.apply(g.contiguous(), ctx.cs), None
+
+
+class _R1Fn(torch.autograd.Function):
+    """r1_reg of the NHWC-4 image gradient g (vst_loss_r1); its backward is a Function too, so create_graph runs
+    through it."""
+
+    @staticmethod
+    def forward(ctx, g):
+        ctx.save_for_backward(g)
+        return ops.r1(g)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (g,) = ctx.saved_tensors
+        return _R1BwdFn.apply(gout.contiguous(), g)
+
+
+class _R1BwdFn(torch.autograd.Function):
+    """u = gout * g / B with lane 3 zeroed: bilinear in (gout, g)."""
+
+    @staticmethod
+    def forward(ctx, gout, g):
+        ctx.save_for_backward(gout, g)
+        return ops.r1_bwd(g, gout)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ggu):
+        gout, g = ctx.saved_tensors
+        ggu = ggu.contiguous()
+        d_gout = d_g = None
+        if ctx.needs_input_grad[0]:   # only a third-order use gets here: the penalty's gout is a constant
+            d_gout = (ggu[..., :3] * g[..., :3]).sum() / g.shape[0]
+        if ctx.needs_input_grad[1]:
+            d_g = ops.r1_bwd(ggu, gout)
+        return d_gout, d_g
+
+
+class _BCEFn(torch.autograd.Function):
+    """adv_loss of the head's output z [B, cpad(num_domains)] at the columns y (vst_loss_bce_logits): the gather,
+    the constant target and the mean in one launch each way; the other columns get exact zeros."""
+
+    @staticmethod
+    def forward(ctx, z, y, nd, target):
+        ctx.save_for_backward(z, y)
+        ctx.conf = (nd, target)
+        return ops.bce_logits(z, y, nd, target)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        z, y = ctx.saved_tensors
+        return ops.bce_logits_bwd(z, y, *ctx.conf, gout.contiguous()), None, None, None
 
 
 # ------------------------------------------------------------------------------------------- parameter holders
@@ -401,16 +590,26 @@ def _trunk(img_size, max_conv_dim):
     return blocks, dim_out
 
 
-def _run_trunk(seq, n_res, img_size, x):
-    """x NCHW [B, 3, img_size, img_size] -> [B, dim_out] (the 4x4 conv's 1x1 output, LeakyReLU applied)."""
-    if x.dim() != 4 or x.shape[2] != img_size or x.shape[3] != img_size:
+def _check_trunk_input(img_size, shape, ax):
+    """shape[ax], shape[ax + 1]: the image's height and width."""
+    if len(shape) != 4 or shape[ax] != img_size or shape[ax + 1] != img_size:
         raise ValueError("this network takes %d x %d images (its 4x4 conv must end at 1x1), got %s"
-                         % (img_size, img_size, tuple(x.shape)))
-    h = _conv(_ToNHWC.apply(x.float(), 4), seq[0])
+                         % (img_size, img_size, tuple(shape)))
+
+
+def _run_trunk_nhwc(seq, n_res, x4):
+    """x4 NHWC [B, img_size, img_size, 4] -> [B, dim_out] (the 4x4 conv's 1x1 output, LeakyReLU applied)."""
+    h = _conv(x4, seq[0])
     for i in range(1, n_res + 1):
         h = seq[i].forward_nhwc(h)
     h = _conv(_LReluFn.apply(h), seq[n_res + 2], "lrelu")
     return h.view(h.shape[0], h.shape[-1])
+
+
+def _run_trunk(seq, n_res, img_size, x):
+    """x NCHW [B, 3, img_size, img_size] -> [B, dim_out]."""
+    _check_trunk_input(img_size, x.shape, 2)
+    return _run_trunk_nhwc(seq, n_res, _ToNHWC2.apply(x.float(), 4))
 
 
 class StyleEncoder(nn.Module):
@@ -438,10 +637,24 @@ class Discriminator(nn.Module):
         blocks.append(_conv2d(dim_out, num_domains, 1, 1, 0))
         self.main = nn.Sequential(*blocks)
 
-    def forward(self, x, y):
-        h = _run_trunk(self.main, self.n_res, self.img_size, x)
+    def head_nhwc(self, x4):
+        """x4 NHWC [B, img_size, img_size, 4] -> every domain's logit [B, cpad(num_domains)] (padding columns 0):
+        what vst_loss_bce_logits gathers from."""
+        _check_trunk_input(self.img_size, x4.shape, 1)
+        if x4.shape[3] != 4:
+            raise ValueError("the NHWC image has 4 lanes (3 channels + padding), got %s" % (tuple(x4.shape),))
+        h = _run_trunk_nhwc(self.main, self.n_res, x4)
         out = _conv(h.view(h.shape[0], 1, 1, h.shape[1]), self.main[self.n_res + 4])
-        return _gather_domain(out.view(out.shape[0], -1)[:, :self.num_domains], y)
+        return out.view(out.shape[0], -1)
+
+    def forward_nhwc(self, x4, y):
+        """forward on the NHWC-4 image: the R1 penalty differentiates with respect to x4, so the image gradient
+        never goes back through NCHW."""
+        return _gather_domain(self.head_nhwc(x4)[:, :self.num_domains], y)
+
+    def forward(self, x, y):
+        _check_trunk_input(self.img_size, x.shape, 2)
+        return self.forward_nhwc(_ToNHWC2.apply(x.float(), 4), y)
 
 
 # ------------------------------------------------------------------------------------- model set, EMA, checkpoints
@@ -523,3 +736,100 @@ class StyleGuided:
                 raise ValueError("StyleGuided: %d style codes for a batch of %d" % (s.shape[0], img.shape[0]))
             s = s.expand(img.shape[0], -1)
         return self.nets.generator(img, s.contiguous())
+
+
+# --------------------------------------------------------------------- the solver's discriminator half
+def he_init(module):
+    """core/utils.py:41-49 on the parameter holders: kaiming-normal (fan_in, relu) weights and zero biases for every
+    conv and Linear; ``net.apply(he_init)``."""
+    if isinstance(module, (Conv2d, Linear)):
+        nn.init.kaiming_normal_(module.weight, mode="fan_in", nonlinearity="relu")
+        if module.bias is not None:
+            nn.init.constant_(module.bias, 0)
+
+
+def _input_grad(out, x, grad_out):
+    """d<out, grad_out>/dx with a graph (create_graph), data gradients only: no weight-gradient kernel runs."""
+    _INPUT_GRAD_ONLY[0] = True
+    try:
+        return torch.autograd.grad(outputs=out, inputs=x, grad_outputs=grad_out, create_graph=True, retain_graph=True,
+                                   only_inputs=True)[0]
+    finally:
+        _INPUT_GRAD_ONLY[0] = False
+
+
+def adv_loss(logits, target):
+    """core/solver.py:459-463: binary_cross_entropy_with_logits against the constant target, mean over all logits."""
+    assert target in [1, 0]
+    z = torch.nn.functional.pad(logits.float().reshape(-1, 1), (0, 3))    # one "domain" per row, padded to a float4
+    return _BCEFn.apply(z, torch.zeros(z.shape[0], dtype=torch.long, device=z.device), 1, target)
+
+
+def r1_reg(d_out, x_in):
+    """core/solver.py:466-476: the zero-centred gradient penalty 0.5 * mean_b ||d sum(d_out) / d x_in[b]||^2 of real
+    images x_in [B, C <= 3, H, W], differentiable with respect to the discriminator's weights."""
+    if x_in.dim() != 4 or x_in.shape[1] > 3:
+        raise NotImplementedError("r1_reg on the HIP path takes images [B, C <= 3, H, W], got %s" % (tuple(x_in.shape),))
+    grad_dout = _input_grad(d_out, x_in, torch.ones_like(d_out))
+    assert grad_dout.size() == x_in.size()
+    return _R1Fn.apply(_ToNHWC2.apply(grad_dout, 4))
+
+
+def _nhwc4(x):
+    return ops.nchw_to_nhwc(x.detach().float().contiguous(), 4)
+
+
+def d_losses(discriminator, x_real, y_org, x_fake, y_trg, lambda_reg):
+    """The arithmetic of compute_d_loss (core/solver.py:360-382) from x_fake on:
+    loss = adv_loss(D(x_real, y_org), 1) + adv_loss(D(x_fake, y_trg), 0) + lambda_reg * r1_reg(D(x_real, y_org), x_real).
+    Returns (loss, attribute dict of the three detached device scalars real / fake / reg).  The images are read, never
+    marked: the penalty differentiates with respect to an NHWC-4 copy of x_real, so x_real.grad stays unset and the
+    image gradient never goes back through NCHW; the domain gather, the target and the mean of each adversarial term
+    are one launch (vst_loss_bce_logits)."""
+    D = discriminator
+    dev = x_real.device
+    y_org, y_trg = (y.to(dev).long().contiguous() for y in (y_org, y_trg))
+    x4 = _nhwc4(x_real).requires_grad_()
+    z = D.head_nhwc(x4)
+    loss_real = _BCEFn.apply(z, y_org, D.num_domains, 1)
+    # d sum_b z[b, y_org[b]] / d x4: the selected logits by comparison, not by index (an id outside the head selects
+    # nothing here and turns the adversarial term into NaN there)
+    sel = (torch.arange(z.shape[1], device=dev)[None] == y_org[:, None]).to(z.dtype)
+    loss_reg = _R1Fn.apply(_input_grad(z, x4, sel).contiguous())
+    loss_fake = _BCEFn.apply(D.head_nhwc(_nhwc4(x_fake)), y_trg, D.num_domains, 0)
+    loss = loss_real + loss_fake + lambda_reg * loss_reg
+    return loss, _AttrDict(real=loss_real.detach(), fake=loss_fake.detach(), reg=loss_reg.detach())
+
+
+def compute_d_loss(nets, args, x_real, y_org, y_trg, z_trg=None, x_ref=None, masks=None):
+    """core/solver.py:360-382: x_fake from the mapping network (z_trg) or the style encoder (x_ref) without gradients,
+    then d_losses.  Returns (loss, attribute dict of the floats real / fake / reg) — one host sync for the three."""
+    assert (z_trg is None) != (x_ref is None)
+    if masks is not None:
+        raise NotImplementedError("masks (the w_hpf > 0 path) are not on the HIP path")
+    with torch.no_grad():
+        s_trg = nets.mapping_network(z_trg, y_trg) if z_trg is not None else nets.style_encoder(x_ref, y_trg)
+        x_fake = nets.generator(x_real, s_trg)
+    loss, parts = d_losses(nets.discriminator, x_real, y_org, x_fake, y_trg, args.lambda_reg)
+    real, fake, reg = torch.stack([parts.real, parts.fake, parts.reg]).tolist()
+    return loss, _AttrDict(real=real, fake=fake, reg=reg)
+
+
+class DiscriminatorTrainer:
+    """The discriminator's side of Solver (core/solver.py:52-61, :167-176): its Adam and the update.  One iteration's
+    D half is ``d_step(..., z_trg=z_trg)`` then ``d_step(..., x_ref=x_ref)``.  args: lr, beta1, beta2, weight_decay,
+    lambda_reg."""
+
+    def __init__(self, nets, args):
+        self.nets, self.args = nets, args
+        self.optimizer = torch.optim.Adam(params=nets.discriminator.parameters(), lr=args.lr,
+                                          betas=[args.beta1, args.beta2], weight_decay=args.weight_decay)
+
+    def d_step(self, x_real, y_org, y_trg, z_trg=None, x_ref=None):
+        """Zero grads, compute_d_loss, backward, step; returns the loss dict.  The backward is asked for D's
+        parameters alone, so nothing is spent on the gradient of the penalty's image copy."""
+        loss, losses = compute_d_loss(self.nets, self.args, x_real, y_org, y_trg, z_trg=z_trg, x_ref=x_ref)
+        self.optimizer.zero_grad()
+        loss.backward(inputs=list(self.nets.discriminator.parameters()))
+        self.optimizer.step()
+        return losses

@@ -549,6 +549,22 @@ int vst_merge_fwd(const float* a, const float* b, float* out, int N, int H, int 
                   void* stream);
 int vst_merge_bwd(const float* g, float* ga, float* gb, int N, int H, int W, int C, int mode, float scale,
                   void* stream);
+/* The losses of StarGAN v2's discriminator update (core/solver.py:459-476), r1.hip.
+ * vst_loss_r1: r1_reg over the NHWC-4 image gradient g [B][hw][4] (lane 3 is padding: read and ignored):
+ * loss = 0.5 / B * sum_{b,p,c<3} g^2, accumulated in fp64 in a fixed order (no float atomics: two runs are
+ * bit-equal).  part: VST_R1_PART_DOUBLES doubles of scratch.  _bwd: u = gout[0] * g / B, lane 3 = 0, gout a device
+ * scalar.  The backward is linear in g, so it is its own second-order operator: d u / d g applied to v is
+ * vst_loss_r1_bwd(v, gout).
+ * vst_loss_bce_logits: adv_loss fused with the domain gather: z [B][D] the head's output (D % 4 == 0, nd <= D real
+ * domains), y [B] int64 device domain ids, target 0 or 1: loss = mean_b (max(v, 0) - v * target + log1p(exp(-|v|))),
+ * v = z[b][y[b]].  _bwd: grad [B][D] = (sigmoid(v) - target) / B * gout[0] in column y[b], 0 elsewhere.  A y[b]
+ * outside [0, nd) is never used as an index: the loss and row b of grad are NaN. */
+enum { VST_R1_PART_DOUBLES = 1024 };
+int vst_loss_r1(const float* g, float* loss, double* part, int B, long hw, void* stream);
+int vst_loss_r1_bwd(const float* g, const float* gout, float* u, int B, long hw, void* stream);
+int vst_loss_bce_logits(const float* z, const long* y, float* loss, int B, int D, int nd, float target, void* stream);
+int vst_loss_bce_logits_bwd(const float* z, const long* y, const float* gout, float* grad, int B, int D, int nd,
+                            float target, void* stream);
 /* U-Net skip connection (UnetSkipConnectionBlock.forward: cat([x, model(x)], 1) under the child's in-place
  * LeakyReLU(slope) and the parent's in-place ReLU).  y [N][HW][C] NHWC; z = (y - mean) * rstd with stats from
  * vst_instnorm_stats, or z = y when stats is NULL (the level below the outermost block, which has no norm).
@@ -814,7 +830,9 @@ int vst_u8_image_to_nhwc4(const unsigned char* x, float* y, long npix, void* str
  *   vst_masked_sqdiff_mean_fwd/bwd   vst_loss_temporal(_bwd)   (fused warp + masked squared diff)
  *   vst_l1_mean_fwd/bwd              vst_loss_l1(_bwd)
  *   vst_mse_const_fwd/bwd            vst_loss_mse_const(_bwd)
- *   vst_gram                         per-image 1x1 vst_conv2d_wgrad + vst_axpby (1/HW)
+ *   vst_r1_fwd/bwd                   vst_loss_r1(_bwd)
+ *   vst_bce_logits_fwd/bwd           vst_loss_bce_logits(_bwd)
+ *   vst_gram                      per-image 1x1 vst_conv2d_wgrad + vst_axpby (1/HW)
  *   vst_corr_volume                  vst_channel_normalize + vst_weight_split + 1x1 vst_conv2d_fwd per
  *                                    image, then vst_corr_pyramid (vst_corr_pyramid / _lookup above)
  *   vst_adam_multi_tensor            vst_adam_step per tensor
@@ -882,6 +900,11 @@ int vst_mse_const_fwd(const float* a, float target, float* loss, float* part, lo
                       void* stream);
 int vst_mse_const_bwd(const float* a, float target, const float* gout, float* grad, long npix, int Cs, int Cl,
                       float scale, void* stream);
+int vst_r1_fwd(const float* g, float* loss, double* part, int B, int H, int W, void* stream);
+int vst_r1_bwd(const float* g, const float* gout, float* u, int B, int H, int W, void* stream);
+int vst_bce_logits_fwd(const float* z, const long* y, float* loss, int B, int D, int nd, float target, void* stream);
+int vst_bce_logits_bwd(const float* z, const long* y, const float* gout, float* grad, int B, int D, int nd,
+                       float target, void* stream);
 
 #ifdef __cplusplus
 }
