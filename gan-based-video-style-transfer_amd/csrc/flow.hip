@@ -209,7 +209,7 @@ extern "C" int vst_warp_masked_fwd(const float* x, const float* flow, float* out
 
 extern "C" int vst_warp_bwd_input(const float* gout, const float* flow, float* gx, int N, int H,
                                   int W, int Cs, int align_corners, void* stream) {
-  VST_REQUIRE(gout && flow && gx && Cs > 0, "warp_bwd_input: bad args");
+  VST_REQUIRE(gout && flow && gx && Cs > 0 && N > 0 && H > 0 && W > 0, "warp_bwd_input: bad args");
   const long total = (long)N * H * W;
   hipLaunchKernelGGL(warp_bwd_k<0>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, gout,
                      flow, gx, N, H, W, Cs, align_corners);
@@ -218,7 +218,7 @@ extern "C" int vst_warp_bwd_input(const float* gout, const float* flow, float* g
 
 extern "C" int vst_warp_masked_bwd_input(const float* gout, const float* flow, float* gx, int N, int H,
                                          int W, int Cs, int align_corners, void* stream) {
-  VST_REQUIRE(gout && flow && gx && Cs > 0, "warp_masked_bwd_input: bad args");
+  VST_REQUIRE(gout && flow && gx && Cs > 0 && N > 0 && H > 0 && W > 0, "warp_masked_bwd_input: bad args");
   const long total = (long)N * H * W;
   hipLaunchKernelGGL(warp_bwd_k<1>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, gout,
                      flow, gx, N, H, W, Cs, align_corners);
@@ -239,7 +239,8 @@ extern "C" int vst_loss_part_floats(long n) { return ceil_div(n, 256) + 1; }
 extern "C" int vst_loss_temporal(const float* a, const float* b, const float* flow,
                                  const float* mask, float* loss, float* part, int N, int H, int W,
                                  int Cs, int Cl, float lambda, void* stream) {
-  VST_REQUIRE(a && b && flow && mask && loss && part && Cl <= Cs, "loss_temporal: bad args");
+  VST_REQUIRE(a && b && flow && mask && loss && part && Cl > 0 && Cl <= Cs && N > 0 && H > 0 && W > 0,
+              "loss_temporal: bad args");
   hipStream_t s = (hipStream_t)stream;
   const long total = (long)N * H * W;
   const int nb = ceil_div(total, 256);
@@ -254,7 +255,8 @@ extern "C" int vst_loss_temporal_bwd(const float* a, const float* b, const float
                                      const float* mask, const float* gout, float* ga, float* gb,
                                      int N, int H, int W, int Cs, int Cl, float lambda,
                                      void* stream) {
-  VST_REQUIRE(a && b && flow && mask && gout && (ga || gb) && Cl <= Cs, "loss_temporal_bwd: bad args");
+  VST_REQUIRE(a && b && flow && mask && gout && (ga || gb) && Cl > 0 && Cl <= Cs && N > 0 && H > 0 && W > 0,
+              "loss_temporal_bwd: bad args");
   const long total = (long)N * H * W;
   const float k = (float)(2.0 * lambda / ((double)total * Cl));
   hipLaunchKernelGGL(temporal_k, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, a, b,
