@@ -8,6 +8,7 @@ gfx950; it is loaded AFTER torch so that it binds to the HIP runtime torch alrea
 import ctypes
 import glob
 import os
+import re
 import subprocess
 
 import torch  # noqa: F401  (must be loaded first: see module docstring)
@@ -19,6 +20,7 @@ LIB_PATH = os.path.join(BUILD, "libvst_hip.so")
 # developer A/B runs only: load an alternative build (tools/build_variant.py) instead
 LIB_PATH = os.environ.get("VST_LIB_VARIANT") or LIB_PATH
 CSRC = os.path.join(PKG, "csrc")
+HEADER = os.path.join(REPO, "include", "vst_hip.h")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -31,7 +33,7 @@ def source_stamp():
     the running code's is not used for its numbers."""
     import hashlib
     h = hashlib.sha1()
-    for f in sorted(glob.glob(os.path.join(CSRC, "*"))) + [os.path.join(REPO, "include", "vst_hip.h")]:
+    for f in sorted(glob.glob(os.path.join(CSRC, "*"))) + [HEADER]:
         if f.endswith((".hip", ".h")):
             h.update(os.path.basename(f).encode())
             h.update(open(f, "rb").read())
@@ -41,207 +43,73 @@ def source_stamp():
     return h.hexdigest()[:12]
 
 
-MATH_MODES = {"fp32": 0, "bf16x3": 1, "bf16x6": 2}  # VST_MATH_* (include/vst_hip.h)
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t}
 
-P = ctypes.c_void_p
-I = ctypes.c_int
-L = ctypes.c_long
-F = ctypes.c_float
-D = ctypes.c_double
-SZ = ctypes.c_size_t
 
-# name -> (restype, argtypes); mirrors include/vst_hip.h
-SIGNATURES = {
-    "vst_last_error": (ctypes.c_char_p, []),
-    "vst_version": (I, []),
-    "vst_build_info": (ctypes.c_char_p, []),
-    "vst_nchw_to_nhwc": (I, [P, P, I, I, I, I, I, P]),
-    "vst_nhwc_to_nchw": (I, [P, P, I, I, I, I, I, P]),
-    "vst_weight_pack": (I, [P, P, I, I, I, I, I, I, I, P]),
-    "vst_conv2d_fwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, P]),
-    "vst_weight_split": (I, [P, P, L, P]),
-    "vst_weight_pack_batch": (I, [P, I, L, P]),
-    "vst_conv2d_fwd_in": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, P, P, P]),
-    "vst_instnorm_finalize": (I, [P, P, I, I, I, I, F, P]),
-    "vst_conv2d_tfwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, F, I, P]),
-    "vst_conv2d_tfwd_co": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, F, I, I, P]),
-    "vst_conv2d_wgrad_bias": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, I, I, P]),
-    "vst_conv2d_wgrad_ws_bytes": (SZ, [I, I, I, I, I, I, I, I, I, I]),
-    "vst_conv2d_wgrad": (I, [P, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, I, I, P]),
-    "vst_debug_set_tiles": (None, [I, I, I]),
-    "vst_conv_plan_fwd": (I, [I, I, I, I, I, I, I, I, I, I, I, P, P, P]),
-    "vst_conv_plan_wgrad": (I, [I, I, I, I, I, I, I, I, I, I, I, P, P, P]),
-    "vst_reflect_fold": (I, [P, P, P, I, I, I, I, I, P]),
-    "vst_channel_sum_ws_bytes": (SZ, [L, I]),
-    "vst_channel_sum": (I, [P, P, P, L, I, I, I, P]),
-    "vst_instnorm_ws_bytes": (SZ, [I, I, I]),
-    "vst_instnorm_stats": (I, [P, P, P, I, I, I, F, P]),
-    "vst_instnorm_act_fwd": (I, [P, P, P, P, I, I, I, I, F, P]),
-    "vst_instnorm_act_bwd": (I, [P, P, P, P, P, P, I, I, I, I, F, I, P]),
-    "vst_instnorm_act_bwd_planes": (I, [P, P, P, P, P, P, I, I, I, I, F, I, P, L, P]),
-    "vst_conv2d_wgrad_nhwc_ok": (I, [I, I, I, I, I, I, I, I, I, I, I, I]),
-    "vst_conv2d_wgrad_nhwc_ws_bytes": (SZ, [I, I, I, I, I, I, I, I, I, I, I, I]),
-    "vst_conv2d_wgrad_nhwc": (I, [P, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, I, I, P]),
-    "vst_conv2d_wgrad_nhwc_f32_ok": (I, [I, I, I, I, I, I, I, I, I, I, I, I]),
-    "vst_conv2d_wgrad_nhwc_f32_ws_bytes": (SZ, [I, I, I, I, I, I, I, I, I, I, I, I]),
-    "vst_conv2d_wgrad_nhwc_f32": (I, [P, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, I, I, P]),
-    "vst_conv2d_wgrad_pre": (I, [P, P, P, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, I, I, I, I, L, L, I, I, P]),
-    "vst_instnorm_act_fwd_cp": (I, [P, P, P, P, P, I, I, I, I, I, F, I, I, I, P]),
-    "vst_instnorm_act_fwd_planes": (I, [P, P, P, P, P, I, I, I, I, I, F, I, I, I, P]),
-    "vst_cp_ld": (L, [L]),
-    "vst_conv2d_fwd_co": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, I, P]),
-    "vst_conv2d_fwd_co_ws_bytes": (SZ, [I, I, I, I, I, I, I, I, I, I, I]),
-    "vst_conv2d_fwd_co_ws": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, I, P, SZ, P]),
-    "vst_tapfold_planes": (I, [P, P, L, I, I, I, I, I, I, I, P]),
-    "vst_conv2d_fwd_ws_bytes": (SZ, [I, I, I, I, I, I, I, I, I, I]),
-    "vst_conv2d_fwd_ws": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, P, P, P, SZ, P]),
-    "vst_c4_dgrad_frame": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "vst_conv_plan_fwd_tail": (I, [I, I, I, I, I, I, I, I, I, I, P]),
-    "vst_act_bwd": (I, [P, P, P, L, I, F, P]),
-    "vst_warp_fwd": (I, [P, P, P, I, I, I, I, I, P]),
-    "vst_warp_bwd_input": (I, [P, P, P, I, I, I, I, I, P]),
-    "vst_fbcheck": (I, [P, P, P, I, I, I, P]),
-    "vst_loss_part_floats": (I, [L]),
-    "vst_loss_temporal": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
-    "vst_loss_temporal_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, P]),
-    "vst_loss_l1": (I, [P, P, P, P, L, I, I, F, P]),
-    "vst_loss_l1_bwd": (I, [P, P, P, P, L, I, I, F, P]),
-    "vst_loss_mse_const": (I, [P, F, P, P, L, I, I, F, P]),
-    "vst_loss_mse_const_bwd": (I, [P, F, P, P, L, I, I, F, P]),
-    "vst_finish_sum": (I, [P, I, P, D, P]),
-    "vst_adam_step": (I, [P, P, P, P, L, F, F, F, F, I, P]),
-    "vst_axpby": (I, [P, P, L, F, F, P]),
-    # learning-based style path / RAFT correlation (style.hip, norm.hip, flow.hip)
-    "vst_warp_masked_fwd": (I, [P, P, P, I, I, I, I, I, P]),
-    "vst_warp_masked_bwd_input": (I, [P, P, P, I, I, I, I, I, P]),
-    "vst_warp_bwd_det_ws_bytes": (SZ, [I, I, I]),
-    "vst_warp_bwd_input_det": (I, [P, P, P, P, SZ, I, I, I, I, I, I, I, I, P]),
-    "vst_temporal_sqdiff_part_floats": (I, [I, I, I, I]),
-    "vst_temporal_sqdiff_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, P]),
-    "vst_temporal_sqdiff_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, P]),
-    "vst_resize_bilinear": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "vst_ruder_stack_fwd": (I, [P, P, P, P, P, P, I, I, I, F, P]),
-    "vst_ruder_stack_bwd": (I, [P, P, P, P, P, I, I, I, F, P]),
-    "vst_ruder_temporal_part_floats": (I, [I, I, I]),
-    "vst_ruder_temporal_fwd": (I, [P, P, P, P, P, I, I, I, F, F, P]),
-    "vst_ruder_temporal_bwd": (I, [P, P, P, P, P, P, I, I, I, F, F, P]),
-    "vst_instnorm_affine_fwd": (I, [P, P, P, P, P, F, P, P, I, I, I, I, F, P]),
-    "vst_instnorm_affine_ws_bytes": (SZ, [I, I, I]),
-    "vst_instnorm_affine_bwd": (I, [P, P, P, P, P, P, F, P, P, P, P, P, P, I, I, I, I, F, I, P]),
-    "vst_cond_instnorm_ws_bytes": (SZ, [I, I, I]),
-    "vst_cond_instnorm_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
-    "vst_cond_instnorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
-    "vst_adain_ws_bytes": (SZ, [I, I, I]),
-    "vst_adain_fwd": (I, [P, P, P, P, P, I, I, I, I, F, P]),
-    "vst_adain_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, F, I, P]),
-    "vst_act_fwd": (I, [P, P, L, I, F, P]),
-    "vst_avgpool2_fwd": (I, [P, P, I, I, I, I, P]),
-    "vst_avgpool2_bwd": (I, [P, P, I, I, I, I, P]),
-    "vst_merge_fwd": (I, [P, P, P, I, I, I, I, I, F, P]),
-    "vst_merge_bwd": (I, [P, P, P, I, I, I, I, I, F, P]),
-    "vst_instnorm_skip_ws_bytes": (SZ, [I, I, I]),
-    "vst_instnorm_skip_fwd": (I, [P, P, P, P, I, I, I, I, I, F, P]),
-    "vst_instnorm_skip_bwd": (I, [P, P, I, I, P, P, P, P, I, P, I, I, I, F, P]),
-    "vst_upsample2x_fwd": (I, [P, P, I, I, I, I, P]),
-    "vst_upsample2x_bwd": (I, [P, P, I, I, I, I, P]),
-    "vst_scaled_tanh_fwd": (I, [P, P, L, I, I, P]),
-    "vst_scaled_tanh_bwd": (I, [P, P, P, L, I, I, P]),
-    "vst_channel_normalize": (I, [P, P, P, P, F, L, I, I, I, P]),
-    "vst_maxpool2_fwd": (I, [P, P, I, I, I, I, P]),
-    "vst_maxpool2_bwd": (I, [P, P, P, I, I, I, I, P]),
-    "vst_loss_mse": (I, [P, P, P, P, L, I, I, F, I, P]),
-    "vst_loss_mse_bwd": (I, [P, P, P, P, L, I, I, F, I, P]),
-    "vst_loss_tv": (I, [P, P, P, I, I, I, I, I, F, I, P]),
-    "vst_loss_tv_bwd": (I, [P, P, P, I, I, I, I, I, F, P]),
-    "vst_gram_sym": (I, [P, P, I, F, P]),
-    "vst_corr_pyramid_floats": (L, [L, I, I, L, I]),
-    "vst_corr_pyramid": (I, [P, L, I, I, L, I, P]),
-    "vst_corr_lookup": (I, [P, P, P, I, I, I, I, I, L, I, I, I, P]),
-    "vst_altcorr_pyramid_floats": (L, [I, I, I, I, I]),
-    "vst_altcorr_pyramid": (I, [P, P, I, I, I, I, I, P]),
-    "vst_altcorr_lookup": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
-    # StarGAN (style.hip, norm.hip)
-    "vst_concat_label_nhwc": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "vst_instnorm_running_update": (I, [P, P, P, I, I, I, F, F, P]),
-    "vst_instnorm_stats_from_running": (I, [P, P, P, I, I, F, P]),
-    "vst_fc2_unpack": (I, [P, P, P, P, P, I, I, I, P]),
-    "vst_weight_pack_split": (I, [P, P, P, I, I, I, I, I, I, I, P]),
-    "vst_conv2d_fwd_hw": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, P]),
-    "vst_conv2d_fwd_hw_ws_bytes": (SZ, [I, I, I, I, I, I, I, I, I, I, I]),
-    "vst_conv2d_fwd_hw_ws": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, I, P, SZ, P]),
-    "vst_conv2d_fwd_hwp": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, I, P]),
-    "vst_tapconv_h_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, I, P]),
-    "vst_tapshift_planes": (I, [P, P, L, I, I, I, I, P]),
-    "vst_tap_wgrad_scatter_h": (I, [P, P, I, I, I, I, I, P]),
-    "vst_conv2d_fwd_phase": (I, [P, P, P, P, I, I, I, I, I, I, I, I, F, I, P]),
-    "vst_conv2d_convT_s2": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P]),
-    "vst_conv4s2_dgrad": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P]),
-    "vst_raft_prep": (I, [P, P, I, I, I, I, I, I, I, P]),
-    "vst_tapsum_fwd": (I, [P, I, P, P, I, I, I, I, I, I, I, I, F, P]),
-    "vst_tapfold": (I, [P, P, I, I, I, I, I, I, I, P]),
-    "vst_tap_wgrad_scatter": (I, [P, P, I, I, I, I, I, P]),
-    "vst_tap_wgrad_swap": (I, [P, P, P, P, SZ, I, I, I, I, I, I, I, I, P]),
-    "vst_tap_wgrad_swap_db": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, I, I, P]),
-    "vst_tap_wgrad_swap_ws_bytes": (SZ, [I, I, I, I, I]),
-    "vst_tap_wgrad_swap_ld": (L, [I, I, I, I]),
-    "vst_tapgather": (I, [P, P, I, I, I, I, I, I, I, P]),
-    "vst_interleave_phases": (I, [P, P, P, P, P, I, I, I, I, P]),
-    "vst_interleave_phases_full": (I, [P, P, P, P, P, I, I, I, I, P]),
-    "vst_raft_prep_nhwc": (I, [P, I, P, I, I, I, I, I, I, I, P]),
-    "vst_loss_masked_l1": (I, [P, P, P, P, P, L, I, I, F, P]),
-    "vst_loss_masked_l1_bwd": (I, [P, P, P, P, P, L, I, I, F, P]),
-    "vst_add_relu": (I, [P, P, P, L, P]),
-    "vst_copy_channels": (I, [P, I, I, P, I, I, I, L, P]),
-    "vst_raft_ctx_split": (I, [P, I, I, I, P, P, P, I, L, P]),
-    "vst_raft_flow4": (I, [P, P, I, I, I, P]),
-    "vst_raft_motion": (I, [P, I, I, P, P, P, I, I, L, P]),
-    "vst_gru_reset": (I, [P, P, P, I, I, L, P]),
-    "vst_gru_update": (I, [P, P, P, P, I, I, L, P]),
-    "vst_raft_coords_update": (I, [P, P, I, I, I, I, P]),
-    "vst_raft_upsample": (I, [P, P, I, P, I, I, I, P]),
-    "vst_u8_image_to_nhwc4": (I, [P, P, L, P]),
-    "vst_conv2d_dgrad_refl_ws_bytes": (SZ, [I, I, I, I, I, I]),
-    "vst_conv2d_dgrad_refl": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, P]),
-    "vst_conv2d_dgrad_refl_in_epi_ws_bytes": (SZ, [I, I, I, I, I, I]),
-    "vst_conv2d_dgrad_refl_in_epi": (I, [P, P, P, P, P, P, P, P, P, SZ, I, I, I, I, I, I, F, I, P, L, I, P]),
-    "vst_conv2d_dgrad_refl_epi_part": (I, [P, P, P, P, P, P, P, P, SZ, I, I, I, I, I, I, F, I, P]),
-    "vst_instnorm_act_bwd_epi_tail": (I, [P, P, P, P, P, P, I, I, I, I, I, F, I, P, L, P, P]),
-    "vst_instnorm_act_bwd_planes_apre": (I, [P, P, P, P, P, P, I, I, I, I, F, I, P, L, P, P]),
-    # SURVEY §8b spelling (abi.hip)
-    "vst_conv_desc_out_hw": (I, [P, P, P]),
-    "vst_workspace_size": (SZ, [P, I]),
-    "vst_conv2d_fwd_desc": (I, [P, P, P, P, P, P, P, P, P, SZ, P]),
-    "vst_conv2d_dgrad_desc": (I, [P, P, P, P, P, P, SZ, P]),
-    "vst_conv2d_wgrad_desc": (I, [P, P, P, P, I, I, I, P, SZ, P]),
-    "vst_adam_multi_tensor": (I, [P, P, P, P, P, I, F, F, F, F, I, P]),
-    "vst_gram_ws_bytes": (SZ, [I, I]),
-    "vst_gram": (I, [P, P, I, I, I, P, SZ, I, P]),
-    "vst_corr_volume_ws_bytes": (SZ, [I, I, I, I]),
-    "vst_corr_volume": (I, [P, P, P, I, I, I, I, I, P, I, P, SZ, I, P]),
-    "vst_warp_bilinear_fwd": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "vst_warp_bilinear_bwd_input": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "vst_masked_sqdiff_mean_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
-    "vst_masked_sqdiff_mean_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, P]),
-    "vst_l1_mean_fwd": (I, [P, P, P, P, L, I, I, F, P]),
-    "vst_l1_mean_bwd": (I, [P, P, P, P, L, I, I, F, P]),
-    "vst_mse_const_fwd": (I, [P, F, P, P, L, I, I, F, P]),
-    "vst_mse_const_bwd": (I, [P, F, P, P, L, I, I, F, P]),
-    "vst_loss_r1": (I, [P, P, P, I, L, P]),
-    "vst_loss_r1_bwd": (I, [P, P, P, I, L, P]),
-    "vst_loss_bce_logits": (I, [P, P, P, I, I, I, F, P]),
-    "vst_loss_bce_logits_bwd": (I, [P, P, P, P, I, I, I, F, P]),
-    "vst_r1_fwd": (I, [P, P, P, I, I, I, P]),
-    "vst_r1_bwd": (I, [P, P, P, I, I, I, P]),
-    "vst_bce_logits_fwd": (I, [P, P, P, I, I, I, F, P]),
-    "vst_bce_logits_bwd": (I, [P, P, P, P, I, I, I, F, P]),
-}
+def _ctype(decl, where, ret=False):
+    """ctypes type of one C parameter, field or return type ('const float* x', 'long n', 'void'): every
+    pointer is c_void_p (a `const char*` return c_char_p), a scalar outside _SCALARS raises."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return ctypes.c_char_p if ret and words[0] == "char" else ctypes.c_void_p
+    if ret and words == ["void"]:
+        return None
+    if words and words[0] in _SCALARS and len(words) == (1 if ret else 2):
+        return _SCALARS[words[0]]
+    raise ValueError("vst_hip.h: %s: no ctypes mapping for %r" % (where, " ".join(decl.split())))
+
+
+def parse_header(text):
+    """The Python view of a C ABI header: (signatures, constants, structs).
+    signatures: name -> (restype, argtypes) of every `<type> vst_name(<params>);`; constants: every
+    `NAME = integer` of the anonymous enums; structs: name -> [(field, ctype)] of every typedef struct.
+    Text that is none of these, and a type _ctype does not know, raises: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    constants, structs, signatures = {}, {}, {}
+
+    def enum(m):
+        for item in filter(None, (i.strip() for i in m.group(1).split(","))):
+            name, eq, val = (p.strip() for p in item.partition("="))
+            if not (eq and re.fullmatch(r"\w+", name)):
+                raise ValueError("vst_hip.h: enum member %r has no explicit value" % item)
+            constants[name] = int(val, 0)
+        return " "
+
+    def struct(m):
+        fields = structs[m.group(2)] = []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+            ctype, _, names = decl.partition(" ")  # `int N, H, W`: one type, several fields
+            fields += [(n.strip(), _ctype(ctype + " " + n, "struct " + m.group(2))) for n in names.split(",")]
+        return " "
+
+    text = re.sub(r"\benum\s*\{([^{}]*)\}\s*;", enum, text)
+    text = re.sub(r"\btypedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    *decls, rest = text.split(";")
+    if rest.strip() not in ("", "}"):
+        raise ValueError("vst_hip.h: text after the last declaration: %r" % rest.strip())
+    for decl in decls:
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(\w+)\s*\(([^()]*)\)\s*", decl)
+        if not m:
+            raise ValueError("vst_hip.h: not a function declaration: %r" % " ".join(decl.split()))
+        ret, name, params = m.groups()
+        params = [] if params.strip() == "void" else params.split(",")
+        signatures[name] = (_ctype(ret, name, ret=True), [_ctype(p, name) for p in params])
+    return signatures, constants, structs
+
+
+# name -> (restype, argtypes); VST_* enum values; struct fields: all read from the header the library is built from
+SIGNATURES, CONSTANTS, STRUCTS = parse_header(open(HEADER).read())
+MATH_MODES = {"fp32": CONSTANTS["VST_MATH_F32"], "bf16x3": CONSTANTS["VST_MATH_BF16X3"],
+              "bf16x6": CONSTANTS["VST_MATH_BF16X6"]}
 
 
 class VstConvDesc(ctypes.Structure):
     """include/vst_hip.h vst_conv_desc."""
-    _fields_ = [(n, ctypes.c_int) for n in ("N", "H", "W", "C", "K", "R", "S", "stride", "pad", "pad_mode",
-                                             "dilation", "transposed", "output_padding", "layout", "dtype",
-                                             "epilogue")] + [("slope", ctypes.c_float), ("math", ctypes.c_int)]
+    _fields_ = STRUCTS["vst_conv_desc"]
 
 
 # Per-file compiler flags.  conv_bf.hip: no SLP vectorisation — it pairs the operand split's fp32
@@ -287,8 +155,7 @@ def build(force=False, verbose=False, out=None, defines=()):
     objdir = os.path.join(os.path.dirname(lib_path), "obj_" + os.path.basename(lib_path)[:-3])
     os.makedirs(objdir, exist_ok=True)
     srcs = sources()
-    deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(REPO, "include", "vst_hip.h"),
-                                                          os.path.abspath(__file__)]
+    deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER, os.path.abspath(__file__)]
     if not force and os.path.exists(lib_path):
         if os.path.getmtime(lib_path) >= max(os.path.getmtime(d) for d in deps):
             return lib_path

@@ -11,12 +11,14 @@ import torch
 
 from . import _lib
 
-ACT = {"none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
-PAD = {"zero": 0, "reflect": 1}
-PACK_KC, PACK_CK, PACK_OK, PACK_IK, PACK_IKF, PACK_SOK = 0, 1, 2, 3, 4, 5
+_C = _lib.CONSTANTS  # the VST_* enum values of include/vst_hip.h
+ACT = {"none": _C["VST_ACT_NONE"], "relu": _C["VST_ACT_RELU"], "lrelu": _C["VST_ACT_LRELU"], "tanh": _C["VST_ACT_TANH"]}
+PAD = {"zero": _C["VST_PAD_ZERO"], "reflect": _C["VST_PAD_REFLECT"]}
+PACK_KC, PACK_CK, PACK_OK, PACK_IK, PACK_IKF, PACK_SOK = (
+    _C["VST_PACK_" + n] for n in ("KC", "CK", "OK", "IK", "IKF", "SOK"))
 # the conv kernels consume: forward conv -> PACK_OK, data-gradient / transposed conv -> PACK_IK
 PACK_FWD, PACK_DGRAD = PACK_OK, PACK_IK
-EUNSUPPORTED = 2  # VST_EUNSUPPORTED (include/vst_hip.h)
+EUNSUPPORTED = _C["VST_EUNSUPPORTED"]
 IN_EPS = 1e-5
 
 
@@ -457,7 +459,7 @@ def debug_set_tiles(fprop=-1, tconv=-1, wgrad=-1):
     lib().vst_debug_set_tiles(*_tiles.v)
 
 
-PLAN_RK, PLAN_SKINNY, PLAN_C4_DIRECT = -1, -2, -3
+PLAN_RK, PLAN_SKINNY, PLAN_C4_DIRECT = _C["VST_PLAN_RK"], _C["VST_PLAN_SKINNY"], _C["VST_PLAN_C4_DIRECT"]
 TILE_NAMES = {0: "128x128 (8 waves of 64x32)", 1: "128x64", 2: "128x128 (4 waves of 64x64)", 3: "64x128",
               4: "128x128 BK64", 5: "128x64 BK64", 6: "64x64", 7: "256x128 (8 waves of 64x64)", 8: "64x64 BK64",
               9: "128x128 BK16 (4 waves of 64x64, 2 blocks/CU at x6)",
@@ -465,9 +467,10 @@ TILE_NAMES = {0: "128x128 (8 waves of 64x32)", 1: "128x64", 2: "128x128 (4 waves
               PLAN_C4_DIRECT: "4-channel patch-staged direct kernel"}
 
 
-WPLAN_BF = 2  # VST_WPLAN_BF: the split-bf16 kernel over channel-major operand images
-WPLAN_NAMES = {0: "conv_wgrad_k (NHWC operands)", 1: "copies + conv_wgrad_rk_k", 2: "copies + conv_wgrad_bf_k",
-               3: "skinny VALU", 4: "Wo-padded copies + conv_wgrad_bf_k"}
+WPLAN_BF = _C["VST_WPLAN_BF"]  # the split-bf16 kernel over channel-major operand images
+WPLAN_NAMES = {_C["VST_WPLAN_GENERIC"]: "conv_wgrad_k (NHWC operands)", _C["VST_WPLAN_RK"]: "copies + conv_wgrad_rk_k",
+               WPLAN_BF: "copies + conv_wgrad_bf_k", _C["VST_WPLAN_SKINNY"]: "skinny VALU",
+               _C["VST_WPLAN_BF_PADW"]: "Wo-padded copies + conv_wgrad_bf_k"}
 
 
 def conv_plan_wgrad(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, math):
@@ -832,7 +835,7 @@ def loss_mse_const_bwd(a, target, gout, scale=1.0, cl=1):
     return g
 
 
-R1_PART_DOUBLES = 1024  # VST_R1_PART_DOUBLES
+R1_PART_DOUBLES = _C["VST_R1_PART_DOUBLES"]
 
 
 def _r1_check(what, g):
@@ -1226,7 +1229,7 @@ def avgpool2_bwd(gy):
     return gx
 
 
-MERGE = {"same": 0, "pool": 1, "up": 2}  # VST_MERGE_*
+MERGE = {"same": _C["VST_MERGE_SAME"], "pool": _C["VST_MERGE_POOL"], "up": _C["VST_MERGE_UP"]}
 
 
 def _merge_b_shape(a_shape, mode):
