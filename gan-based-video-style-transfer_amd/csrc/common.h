@@ -134,6 +134,7 @@ int skinny_out_launch(int mode, const float* in, const float* wp, const float* b
                       const float* addend, float* out, int N, int Hi, int Wi, int Cin, int Ho,
                       int Wo, int R, int S, int st, int pad, int reflect, int act, float slope,
                       hipStream_t s, int co_real = 4);
+bool skinny_split_plan(int mode, long pix, int R, int S, int Cin, int* CC_out, int* nsplit_out);
 // [row][k]-LDS implicit-GEMM fprop / transposed conv (conv_rk.hip); kind = tile override or -1
 // (padh, padw: zero/reflect padding rows / columns — the forward kernels take them separately)
 void rk_fprop_launch(const float* x, const float* wp, const float* bias, float* y, int N, int H, int W,

@@ -1067,6 +1067,9 @@ extern "C" int vst_conv4s2_dgrad(const float* dy, const void* ws00, const void* 
                                 1);
 }
 
+// vst_conv2d_tfwd's kernel: image-channel (4-channel) outputs on the VALU path, everything else on the [row][k] kernel
+static int tfwd_plan(int Cx) { return Cx == 4 ? VST_PLAN_SKINNY : VST_PLAN_RK; }
+
 extern "C" int vst_conv2d_tfwd(const float* in, const float* wp, const float* bias,
                                const float* addend, float* out, int N, int Hi, int Wi, int Cy,
                                int Ho, int Wo, int Cx, int R, int S, int stride, int pad,
@@ -1082,7 +1085,7 @@ extern "C" int vst_conv2d_tfwd(const float* in, const float* wp, const float* bi
   hipStream_t s = (hipStream_t)stream;
   const int Hc = (Ho + stride - 1) / stride, Wc = (Wo + stride - 1) / stride;
   const int Mmax = N * Hc * Wc;
-  if (Cx == 4)  // image-channel data gradients: VALU path (skinny.hip)
+  if (tfwd_plan(Cx) == VST_PLAN_SKINNY)  // image-channel data gradients: VALU path (skinny.hip)
     return skinny_out_launch(1, in, wp, bias, addend, out, N, Hi, Wi, Cy, Ho, Wo, R, S, stride, pad,
                              refl, act, slope, s);
 #define VST_TCONV_ST(BM_, BN_, WM_, WN_, ST_)                                                      \
@@ -1158,6 +1161,39 @@ extern "C" int vst_conv_plan_wgrad(int N, int H, int W, int Cx, int Ho, int Wo, 
   *kind = (int)p.tile;
   *nsplit = p.nsplit;
   return VST_OK;
+}
+
+extern "C" int vst_conv_plan_wgrad_chunk(int N, int H, int W, int Cx, int Ho, int Wo, int Cyp, int R, int S,
+                                         int stride, int math, int* chunk, int* row_w) {
+  VST_REQUIRE(chunk && row_w && N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && R > 0 && S > 0,
+              "conv_plan_wgrad_chunk: bad args");
+  const WgradPlan p = plan_wgrad(N, H, W, Ho, Wo, Cx, Cyp, R, S, stride, math);
+  *chunk = p.chunk;
+  *row_w = Wo + p.wpad;
+  return VST_OK;
+}
+
+// Host-only route queries: the conditions the launches themselves test, for callers and tests that must know which
+// kernel a shape takes.
+extern "C" int vst_conv_plan_tfwd(int Cx, int* plan) {
+  VST_REQUIRE(plan && Cx > 0, "conv_plan_tfwd: bad args");
+  *plan = tfwd_plan(Cx);
+  return VST_OK;
+}
+
+extern "C" int vst_tap64_ok(int Cx, int R, int W, int math) { return tap64_ok(Cx, R, W, math) ? 1 : 0; }
+
+extern "C" int vst_head_ok(int Cin, int R, int S, int stride, int pad_mode, int Wo) {
+  return g_head && head_ok(Cin, R, S, stride, pad_mode == VST_PAD_REFLECT, Wo) ? 1 : 0;
+}
+
+extern "C" int vst_img_wgrad_ok(int Cx, int Cyp, int R, int S, int stride, int pad_mode, int Ci, int Wo) {
+  return g_img_wgrad && img_wgrad_ok(Cx, Cyp, R, S, stride, pad_mode == VST_PAD_REFLECT, Ci, Wo) ? 1 : 0;
+}
+
+extern "C" int vst_skinny_split_ok(int N, int Ho, int Wo, int Cx, int R, int S) {
+  int cc, ns;
+  return skinny_split_plan(0, (long)N * Ho * Wo, R, S, Cx, &cc, &ns) ? 1 : 0;
 }
 
 extern "C" size_t vst_conv2d_wgrad_ws_bytes(int N, int H, int W, int Cx, int Ho, int Wo, int Cyp,

@@ -283,6 +283,18 @@ static constexpr bool g_skinny_split = true;
 // the PatchGAN head's one-channel forward on its row kernel (patch.hip); g_head = false: the per-pixel gather here
 const bool g_head = true;
 
+// Does a forward (mode 0) over `pix` output pixels take skinny_split_k, and with which channel chunk / split count?
+bool skinny_split_plan(int mode, long pix, int R, int S, int Cin, int* CC_out, int* nsplit_out) {
+  if (!(mode == 0 && g_skinny_split && pix * 16 <= 4096 && (long)R * S * Cin >= 4096 && Cin % 64 == 0)) return false;
+  int CC = Cin;
+  while (CC > 256 && CC % 2 == 0 && (CC / 2) % 64 == 0) CC /= 2;
+  const int nsplit = R * S * (Cin / CC);
+  if ((long)nsplit * pix * 4 > SKINNY_SLAB) return false;
+  *CC_out = CC;
+  *nsplit_out = nsplit;
+  return true;
+}
+
 int skinny_out_launch(int mode, const float* in, const float* wp, const float* bias,
                       const float* addend, float* out, int N, int Hi, int Wi, int Cin, int Ho,
                       int Wo, int R, int S, int st, int pad, int reflect, int act, float slope,
@@ -307,12 +319,10 @@ int skinny_out_launch(int mode, const float* in, const float* wp, const float* b
   }
   if (mode == 0 && co_real == 1 && g_head && head_ok(Cin, R, S, st, reflect, Wo) && !addend)
     return head_fwd_launch(in, wp, bias, out, N, Hi, Wi, Cin, Ho, Wo, R, S, pad, act, slope, s);
-  if (mode == 0 && g_skinny_split && pix * 16 <= 4096 && (long)R * S * Cin >= 4096 && Cin % 64 == 0) {
+  {
     // few pixels, long K: split the K range over workgroups (skinny_split_k)
-    int CC = Cin;
-    while (CC > 256 && CC % 2 == 0 && (CC / 2) % 64 == 0) CC /= 2;
-    const int nsplit = R * S * (Cin / CC);
-    if ((long)nsplit * pix * 4 <= SKINNY_SLAB) {
+    int CC, nsplit;
+    if (skinny_split_plan(mode, pix, R, S, Cin, &CC, &nsplit)) {
       hipLaunchKernelGGL(skinny_split_k<16>, dim3(ceil_div(pix * 16, 256), nsplit), dim3(256), 0, s, in, wp, N, Hi, Wi,
                          Cin, Ho, Wo, S, st, pad, reflect, CC);
       hipLaunchKernelGGL(skinny_split_reduce_k, dim3(ceil_div(pix, 256)), dim3(256), 0, s, bias, addend, out, pix,

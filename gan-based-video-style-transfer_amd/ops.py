@@ -1865,17 +1865,24 @@ def conv4s2_dgrad_phase_packs(w):
 C4S2_GROUPED = True
 
 
+def conv4s2_dgrad_grouped(N, Hd, Wd, Cy, cop, role="bwd", split=True):
+    """Does conv4s2_dgrad run its one grouped launch (vst_conv4s2_dgrad) for this shape?  split: the packs carry
+    their bf16 planes.  A grid of fewer than half a CU round of 128x128 phase tiles (the StarGAN discriminator's
+    deep layers: 100 rows x 1024 channels per phase at B = 4, K = 8192) runs as four split-K forwards + the
+    interleave instead."""
+    small = 4 * (-(-N * (Hd + 1) * (Wd + 1) // 128)) * (-(-cop // 128)) < 128
+    return bool(C4S2_GROUPED and _math(role) != _lib.MATH_MODES["fp32"] and Cy % 32 == 0 and cop != 4 and not small
+                and split)
+
+
 def conv4s2_dgrad(dy, packs, cop, role="bwd"):
     """Data gradient of Conv2d(k=4, s=2, p=1) onto a (2*Hd) x (2*Wd) input via four 2x2 phase convs
     (padding 1, outputs (Hd+1) x (Wd+1)) + vst_interleave_phases_full."""
     _dev_check(dy)
     N, Hd, Wd, Cy = dy.shape
     m = _math(role)
-    # a grid of fewer than half a CU round of 128x128 phase tiles (the StarGAN discriminator's deep layers: 100
-    # rows x 1024 channels per phase at B = 4, K = 8192) runs as four split-K forwards + the interleave instead
-    small = 4 * (-(-N * (Hd + 1) * (Wd + 1) // 128)) * (-(-cop // 128)) < 128
-    if C4S2_GROUPED and m != _lib.MATH_MODES["fp32"] and Cy % 32 == 0 and cop != 4 and not small and \
-            all(getattr(wp, "vst_split", None) is not None for wp in packs):
+    split = all(getattr(wp, "vst_split", None) is not None for wp in packs)
+    if conv4s2_dgrad_grouped(N, Hd, Wd, Cy, cop, role, split):
         # one launch, stored straight into the interleaved gradient (vst_conv4s2_dgrad)
         y = torch.empty((N, 2 * Hd, 2 * Wd, cop), device=dy.device)
         _call("vst_conv4s2_dgrad", _p(dy), *[_p(wp.vst_split) for wp in packs], _p(y), N, Hd, Wd, Cy, cop, m,
@@ -1912,16 +1919,25 @@ CONVT_DIRECT = True
 CONVT_GROUPED = True
 
 
+def convT3s2_route(Cx, cop, role="fwd", split=True):
+    """The form convT3s2_fwd runs: 'grouped' (vst_conv2d_convT_s2, all four phases in one launch), 'phase'
+    (vst_conv2d_fwd_phase per phase) or 'images' (phase images + vst_interleave_phases).  split: the packs carry
+    their bf16 planes."""
+    if not (CONVT_DIRECT and _math(role) != _lib.MATH_MODES["fp32"] and Cx % 8 == 0 and cop != 4 and split):
+        return "images"
+    return "grouped" if CONVT_GROUPED and Cx % 32 == 0 else "phase"
+
+
 def convT3s2_fwd(x, packs, bias, cop, act="none", role="fwd"):
     """ConvTranspose2d(k=3, s=2, p=1, op=1) forward on NHWC x via four phase convs, stored straight into
     the interleaved output (split-bf16 math) or as phase images + interleave."""
     _dev_check(x, bias)
     N, H, W, Cx = x.shape
     m = _math(role)
-    if CONVT_DIRECT and m != _lib.MATH_MODES["fp32"] and Cx % 8 == 0 and cop != 4 and \
-            all(getattr(wp, "vst_split", None) is not None for wp in packs):
+    route = convT3s2_route(Cx, cop, role, all(getattr(wp, "vst_split", None) is not None for wp in packs))
+    if route != "images":
         y = torch.empty((N, 2 * H, 2 * W, cop), device=x.device)
-        if CONVT_GROUPED and Cx % 32 == 0:
+        if route == "grouped":
             _call("vst_conv2d_convT_s2", _p(x), *[_p(wp.vst_split) for wp in packs], _p(bias), _p(y), N, H, W, Cx,
                   cop, ACT[act], 0.0, m, _stream())
             return y

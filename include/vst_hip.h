@@ -311,6 +311,22 @@ int vst_conv_plan_fwd(int N, int H, int W, int Cx, int Cop, int R, int S, int st
 enum { VST_WPLAN_GENERIC = 0, VST_WPLAN_RK = 1, VST_WPLAN_BF = 2, VST_WPLAN_SKINNY = 3, VST_WPLAN_BF_PADW = 4 };
 int vst_conv_plan_wgrad(int N, int H, int W, int Cx, int Ho, int Wo, int Cyp, int R, int S, int stride,
                         int math, int* path, int* kind, int* nsplit);
+/* Host-only: of the same plan, *chunk = output pixels per split-K slab, counted over output rows of *row_w
+ * columns (Wo, or Wo padded to a multiple of 8 on VST_WPLAN_BF_PADW): slab z takes pixels [z chunk, (z+1) chunk). */
+int vst_conv_plan_wgrad_chunk(int N, int H, int W, int Cx, int Ho, int Wo, int Cyp, int R, int S, int stride,
+                              int math, int* chunk, int* row_w);
+/* Host-only route queries (no launch, no device needed), each the condition the launch itself tests:
+ * vst_conv_plan_tfwd: *plan = VST_PLAN_SKINNY (Cx == 4, VALU) or VST_PLAN_RK ([row][k] kernel) of vst_conv2d_tfwd;
+ * vst_tap64_ok: does vst_tapconv_h_fwd run the direct 64-channel 7 x 7 kernel (conv_tap64.hip) for this width;
+ * vst_head_ok: do the one-real-channel head kernels (patch.hip) take vst_conv2d_fwd_co / _tfwd_co / the weight
+ *   gradient with Co = 1 (Wo: the output width; for _tfwd_co the width of dy);
+ * vst_img_wgrad_ok: does vst_conv2d_wgrad take the image-input kernel (patch.hip);
+ * vst_skinny_split_ok: does a forward with 4 output channels run as K-range splits (skinny_split_k). */
+int vst_conv_plan_tfwd(int Cx, int* plan);
+int vst_tap64_ok(int Cx, int R, int W, int math);
+int vst_head_ok(int Cin, int R, int S, int stride, int pad_mode, int Wo);
+int vst_img_wgrad_ok(int Cx, int Cyp, int R, int S, int stride, int pad_mode, int Ci, int Wo);
+int vst_skinny_split_ok(int N, int Ho, int Wo, int Cx, int R, int S);
 /* db[c] (+)= sum over NHW pixels of x[p][c] for c < Cl (channel stride Cs); bias gradient of a layer
  * whose output gradient is x.  ws: vst_channel_sum_ws_bytes bytes; fixed-order (deterministic). */
 size_t vst_channel_sum_ws_bytes(long NHW, int Cs);

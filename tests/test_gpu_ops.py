@@ -7,7 +7,11 @@ absolute.
 
 The reduction families (InstanceNorm stats / forward / backward in every slice geometry, affine
 InstanceNorm, running statistics, the scalar losses and axpby) are checked per plane against fp64
-references in tests/test_gpu_reductions.py; this file keeps one shape of each."""
+references in tests/test_gpu_reductions.py; this file keeps one shape of each.
+
+The conv ARITHMETIC (all six plane products of bf16x6 issued on every route and tile kind, the tap / channel /
+phase / mirror addressing, no K stage skipped) is pinned in tests/test_gpu_conv_arith.py: bit-exact one-product
+probes and a per-output bound c u B(o); the global max|ref| tolerance here cannot tell bf16x6 from bf16x3."""
 import numpy as np
 import pytest
 import torch
