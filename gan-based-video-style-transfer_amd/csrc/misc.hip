@@ -307,7 +307,9 @@ extern "C" int vst_weight_pack_batch(const void* jobs, int njobs, long nblocks, 
 
 extern "C" int vst_adam_step(float* p, const float* g, float* m, float* v, long n, float lr,
                              float beta1, float beta2, float eps, int step, void* stream) {
-  VST_REQUIRE(p && g && m && v && step >= 1, "adam_step: bad args");
+  VST_REQUIRE(n >= 0 && step >= 1, "adam_step: bad args");
+  if (n == 0) return VST_OK;  // nothing to do (an empty tensor has no pointer); a zero-block grid is a launch error
+  VST_REQUIRE(p && g && m && v, "adam_step: null pointer");
   const double bc1 = 1.0 - pow((double)beta1, step);
   const double bc2 = 1.0 - pow((double)beta2, step);
   hipLaunchKernelGGL(adam_k, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
@@ -316,7 +318,9 @@ extern "C" int vst_adam_step(float* p, const float* g, float* m, float* v, long 
 }
 
 extern "C" int vst_axpby(const float* x, float* y, long n, float a, float b, void* stream) {
-  VST_REQUIRE(x && y, "axpby: bad args");
+  VST_REQUIRE(n >= 0, "axpby: bad args");
+  if (n == 0) return VST_OK;
+  VST_REQUIRE(x && y, "axpby: null pointer");
   hipLaunchKernelGGL(axpby_k, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, a, b);
   return check_launch("axpby");
 }

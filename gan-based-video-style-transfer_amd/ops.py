@@ -1574,13 +1574,26 @@ def raft_motion(out, nout, flow4, hx, rhx, c0):
           _stream())
 
 
+def _gru_check(what, zr, h, q=None):
+    """The GRU kernels take no channel strides: zr is [P][2*hd] and h, q are [P][hd], densely packed (a conv
+    output whose padded width is not 2*hd would be read skewed)."""
+    hd = h.shape[-1]
+    if zr.shape[-1] != 2 * hd or zr.numel() != 2 * h.numel():
+        raise ValueError("%s: zr %s must be [..., 2*hd] over h's pixels, h is %s"
+                         % (what, tuple(zr.shape), tuple(h.shape)))
+    if q is not None and tuple(q.shape) != tuple(h.shape):
+        raise ValueError("%s: q %s and h %s differ" % (what, tuple(q.shape), tuple(h.shape)))
+
+
 def gru_reset(zr, h, rhx):
+    _gru_check("gru_reset", zr, h)
     _dev_check(zr, h, rhx)
     hd = h.shape[-1]
     _call("vst_gru_reset", _p(zr), _p(h), _p(rhx), hd, rhx.shape[-1], h.numel() // hd, _stream())
 
 
 def gru_update(zr, q, h, hx):
+    _gru_check("gru_update", zr, h, q)
     _dev_check(zr, q, h, hx)
     hd = h.shape[-1]
     _call("vst_gru_update", _p(zr), _p(q), _p(h), _p(hx), hd, hx.shape[-1], h.numel() // hd, _stream())

@@ -446,10 +446,11 @@ int vst_finish_sum(const float* part, int n, float* out, double scale, void* str
 /* ---- optimizer ------------------------------------------------------------------------------ */
 /* torch.optim.Adam (no weight decay, no amsgrad) over a flat parameter buffer:
  *   m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
- *   p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)                                    */
+ *   p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+ * n == 0 returns VST_OK without a launch (the pointers may then be null); n < 0 is an error.   */
 int vst_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
                   float beta2, float eps, int step, void* stream);
-/* y = a*x + b*y over n floats (gradient scaling / DP averaging helper). */
+/* y = a*x + b*y over n floats (gradient scaling / DP averaging helper); n == 0 as vst_adam_step. */
 int vst_axpby(const float* x, float* y, long n, float a, float b, void* stream);
 
 /* ---- learning-based style path -------------------------------------- */
@@ -805,7 +806,9 @@ int vst_raft_flow4(const float* coords1, float* flow4, int B, int h, int w, void
 int vst_raft_motion(const float* out, int ocs, int nout, const float* flow4, float* hx, float* rhx, int xcs,
                     int c0, long npix, void* stream);
 /* SepConvGRU halves (update.py:46-58): rhx[:, :hd] = sigmoid(zr[:, hd:]) * h, and
- * h = (1 - z) h + z q with z = sigmoid(zr[:, :hd]) (also into hx[:, :hd]). */
+ * h = (1 - z) h + z q with z = sigmoid(zr[:, :hd]) (also into hx[:, :hd]).
+ * zr is [npix][2*hd] and h, q are [npix][hd], densely packed: they take no stride (a conv output padded to
+ * another width must not be passed); only hx / rhx carry the channel stride xcs. */
 int vst_gru_reset(const float* zr, const float* h, float* rhx, int hd, int xcs, long npix, void* stream);
 int vst_gru_update(const float* zr, const float* q, float* h, float* hx, int hd, int xcs, long npix, void* stream);
 /* raft.py:127: coords1 += delta_flow (delta NHWC, channels 0/1 of stride dcs). */
