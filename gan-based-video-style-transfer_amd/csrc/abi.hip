@@ -53,12 +53,13 @@ extern "C" size_t vst_workspace_size(const vst_conv_desc* d, int op) {
   switch (op) {
     case VST_OP_FWD:
       return d->transposed ? 0
-                           : vst_conv2d_fwd_ws_bytes(d->N, d->H, d->W, d->C, d->K, d->R, d->S, d->stride, d->pad,
-                                                     d->math);
+                           : vst_conv2d_fwd_ex_ws_bytes(d->N, d->H, d->W, d->C, d->K, d->R, d->S, d->stride, d->pad,
+                                                        d->pad, d->pad_mode, d->math, d->K);
     case VST_OP_DGRAD:
       // a conv's data gradient runs the gather-form transposed kernel (no workspace); a transposed
       // conv's data gradient is a forward conv over its output gradient
-      return d->transposed ? vst_conv2d_fwd_ws_bytes(d->N, Ho, Wo, d->K, d->C, d->R, d->S, d->stride, d->pad, d->math)
+      return d->transposed ? vst_conv2d_fwd_ex_ws_bytes(d->N, Ho, Wo, d->K, d->C, d->R, d->S, d->stride, d->pad,
+                                                        d->pad, VST_PAD_ZERO, d->math, d->C)
                            : 0;
     case VST_OP_WGRAD:
       return d->transposed ? vst_conv2d_wgrad_ws_bytes(d->N, Ho, Wo, d->K, d->H, d->W, d->C, d->R, d->S, d->stride)
@@ -79,8 +80,8 @@ extern "C" int vst_conv2d_fwd_desc(const vst_conv_desc* d, const float* x, const
     return vst_conv2d_tfwd(x, wp, bias, nullptr, y, d->N, d->H, d->W, d->C, Ho, Wo, d->K, d->R, d->S, d->stride,
                            d->pad, VST_PAD_ZERO, d->epilogue, d->slope, d->math, stream);
   }
-  return vst_conv2d_fwd_ws(x, wp, wsplit, bias, y, d->N, d->H, d->W, d->C, d->K, d->R, d->S, d->stride, d->pad,
-                           d->pad_mode, d->epilogue, d->slope, d->math, in_part, in_nsplit, ws, ws_bytes, stream);
+  return vst_conv2d_fwd_ex(x, wp, wsplit, bias, y, d->N, d->H, d->W, d->C, d->K, d->R, d->S, d->stride, d->pad, d->pad,
+                           d->pad_mode, d->epilogue, d->slope, d->math, d->K, in_part, in_nsplit, ws, ws_bytes, stream);
 }
 
 extern "C" int vst_conv2d_dgrad_desc(const vst_conv_desc* d, const float* dy, const float* wp, const void* wsplit,
@@ -89,8 +90,9 @@ extern "C" int vst_conv2d_dgrad_desc(const vst_conv_desc* d, const float* dy, co
   int Ho, Wo;
   out_hw(d, &Ho, &Wo);
   if (d->transposed)  // dx = conv(dy, W seen as a Conv2d weight [Ci_T][Co_T]): wp = its VST_PACK_OK pack
-    return vst_conv2d_fwd_ws(dy, wp, wsplit, nullptr, dx, d->N, Ho, Wo, d->K, d->C, d->R, d->S, d->stride, d->pad,
-                             VST_PAD_ZERO, VST_ACT_NONE, 0.f, d->math, nullptr, nullptr, ws, ws_bytes, stream);
+    return vst_conv2d_fwd_ex(dy, wp, wsplit, nullptr, dx, d->N, Ho, Wo, d->K, d->C, d->R, d->S, d->stride, d->pad,
+                             d->pad, VST_PAD_ZERO, VST_ACT_NONE, 0.f, d->math, d->C, nullptr, nullptr, ws, ws_bytes,
+                             stream);
   // dx = transposed gather of dy with the VST_PACK_IK pack (reflect padding folded in-kernel)
   return vst_conv2d_tfwd(dy, wp, nullptr, nullptr, dx, d->N, Ho, Wo, d->K, d->H, d->W, d->C, d->R, d->S, d->stride,
                          d->pad, d->pad_mode, VST_ACT_NONE, 0.f, d->math, stream);

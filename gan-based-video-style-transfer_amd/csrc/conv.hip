@@ -1,32 +1,24 @@
-// Implicit-GEMM convolution kernels on gfx950 fp32 MFMA (v_mfma_f32_32x32x2_f32).
+// The fp32-MFMA generic weight gradient, the split-K reductions, the reflect-pad fold, the conv planners and
+// the conv entry points of the C ABI.
 //
-// Replaces the cuDNN conv fprop / dgrad / wgrad that nn.Conv2d, nn.ConvTranspose2d and
-// nn.ReflectionPad2d dispatch in the reference ResnetGenerator / NLayerDiscriminator
-// (methods/GAN-based/CycleGAN/models/networks.py:340-367, 404-426, 556-578).
+// Forward convs and data gradients run in conv_bf.hip (split-bf16 implicit GEMM), conv_rk.hip (the [row][k]
+// kernels: rk_fprop_launch, rk_tconv_launch), conv_c4.hip / conv_tap64.hip (the direct image-layer kernels) and
+// skinny.hip / patch.hip (at most 4 output channels); this file decides which (vst_conv_plan_fwd, conv_fwd_impl,
+// plan_wgrad) and holds the one kernel family those files do not replace:
 //
-// Every kernel computes C[BM x BN] = sum_k A[m][k] * B[k][n] per workgroup with
-//   * NW = 4 or 8 waves (256/512 threads), each owning a WM x WN sub-tile of 32x32 MFMA blocks;
-//     a 128x128 tile with 8 waves gives two waves per SIMD inside one workgroup, which is what the
-//     CycleGAN shapes need (B=4: a 16384x256 output is exactly one 128x128 tile per CU);
-//   * BK = 32 deep K-steps double-buffered in LDS, one barrier per K-step.  Both LDS operand images
-//     are k-major ([k][row], +4 float pad) so every MFMA operand fetch is a conflict-free ds_read
-//     over 32 consecutive rows; fragments of step kk+2 are fetched while step kk's MFMAs issue;
-//   * the global loads of the NEXT K-step are interleaved into the MFMA sequence of the current
-//     one (2 per MFMA group, so their address arithmetic runs in the shadow of the 64-cycle fp32
-//     MFMAs) and written to the other LDS buffer after the last MFMA group;
-// Operand gathers fold padding (zero or reflect), stride and transposition into address
-// generation: no im2col, no padded copies, no zero-insertion.  fp32 MFMA is an exact fp32 fma
-// chain, so results differ from the CPU reference only by summation order.
-//
-//   conv_fprop_k : y = conv(x, w)            m = output pixel, n = out channel, k = (r, s, ci)
-//   conv_tconv_k : transposed conv / dgrad    gathered per output-parity class (blockIdx.z) so a
-//                  stride-2 layer walks only the taps that hit each class; for stride 1 with
-//                  reflect padding the gather adds the mirrored contributions of ReflectionPad2d's
-//                  backward directly (no padded gradient buffer, no fold pass); optional residual
-//                  addend fused in the epilogue
-//   conv_wgrad_k : dw = x_gather^T * dy       m = (r, s, ci), n = out channel, k = pixel;
-//                  split-K over blockIdx.z into an fp32 slab, summed in a fixed split order
-//                  (deterministic) and written to [Co][Ci][R][S] by wgrad_reduce_store_k.
+//   conv_wgrad_k : dw = x_gather^T * dy on v_mfma_f32_32x32x2_f32, m = (r, s, ci), n = out channel, k = pixel —
+//                  the weight gradients no channel-major or NHWC route takes (plan_wgrad's last arm).
+//                  C[BM x BN] = sum_k A[m][k] * B[k][n] per workgroup: NW = 4 or 8 waves, each owning a WM x WN
+//                  sub-tile of 32x32 MFMA blocks; BK = 32 deep K-steps double-buffered in LDS, one barrier per
+//                  K-step.  Both LDS operand images are k-major ([k][row], +4 float pad) so every MFMA operand
+//                  fetch is a conflict-free ds_read over 32 consecutive rows; the global loads of the NEXT K-step
+//                  are interleaved into the MFMA sequence of the current one (2 per MFMA group) and written to
+//                  the other LDS buffer after the last group.  The gather folds padding (zero or reflect) and
+//                  stride into address generation: no im2col.  fp32 MFMA is an exact fp32 fma chain, so results
+//                  differ from the CPU reference only by summation order.
+//   wgrad_reduce_store_k / slab_group_sum_k : every weight-gradient route's split-K slabs (blockIdx-z pixel
+//                  chunks, fp32) summed in a fixed split order (deterministic) and written to [Co][Ci][R][S].
+//   reflect_fold_k : ReflectionPad2d's backward over a padded gradient (vst_reflect_fold).
 #include "common.h"
 
 namespace vst {
@@ -101,7 +93,7 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[MI][NI]) {
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 }
 
-// Double-buffered K loop shared by all kernels.  load_one(i, k0) issues global load number i
+// Double-buffered K loop.  load_one(i, k0) issues global load number i
 // (0 <= i < NLOAD, compile-time after unrolling) of the stage starting at k0 into registers;
 // adv() steps the incremental index state by BK; store(buf) writes the staged registers to LDS.
 template <int BM, int BN, int WM, int WN, int NLOAD, class LoadOne, class Adv, class Store>
@@ -134,299 +126,8 @@ __device__ __forceinline__ void main_loop(float* smem, int nk, int kbase,
   }
 }
 
-// XCD-aware remap of the M-tile index: consecutive M tiles (neighbouring pixel rows, which share
-// halo rows) land on the same XCD / L2 (blocks b and b+8 share an XCD under round-robin dispatch).
-__device__ __forceinline__ int remap_mtile(int bx, int nx) {
-  if ((nx & 7) != 0) return bx;
-  return (bx & 7) * (nx >> 3) + (bx >> 3);
-}
-
-// transposing store of a thread's float4 A chunk (4 consecutive k of one row m) into [k][m]
-template <int LDA>
-__device__ __forceinline__ void store_a_t(float* As, int kr, int ml, const float4& v) {
-  As[(kr + 0) * LDA + ml] = v.x;
-  As[(kr + 1) * LDA + ml] = v.y;
-  As[(kr + 2) * LDA + ml] = v.z;
-  As[(kr + 3) * LDA + ml] = v.w;
-}
-
 __device__ __forceinline__ void add4(float4& a, const float4& b) {
   a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-}
-
-// ------------------------------------------------------------------------------------------ fprop
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__((Tile<BM, BN, WM, WN>::NT), 2) void conv_fprop_k(
-    const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ bias,
-    float* __restrict__ y, int H, int W, int C, int Ho, int Wo, int Cop, int S, int st, int pad,
-    int reflect, int act, float slope, int M, int Ktot) {
-  using T = Tile<BM, BN, WM, WN>;
-  constexpr int NT = T::NT;
-  constexpr int KSTEP4 = NT / BM;         // k4 stride between a thread's A loads
-  constexpr int A_LD = BK / 4 / KSTEP4;   // float4 A loads per thread per stage
-  constexpr int BN4 = BN / 4;
-  constexpr int KRSTEP = NT / BN4;
-  constexpr int B_LD = BK / KRSTEP;
-  static_assert(NT % BM == 0 && A_LD >= 1 && B_LD >= 1, "tile shape");
-  __shared__ __attribute__((aligned(16))) float smem[2 * T::STAGE];
-
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int mt = remap_mtile(blockIdx.x, gridDim.x);
-  const int m0 = mt * BM, n0 = blockIdx.y * BN;
-
-  const int ml = t % BM, k4b = t / BM;
-  const int m = m0 + ml;
-  const bool mval = m < M;
-  int hb = 0, wb = 0;
-  const float* xb = x;
-  if (mval) {
-    const int hw = Ho * Wo;
-    const int n = m / hw, rem = m - n * hw, ho = rem / Wo, wo = rem - ho * Wo;
-    hb = ho * st - pad;
-    wb = wo * st - pad;
-    xb = x + (long)n * H * W * C;
-  }
-  int ac[A_LD], as_[A_LD], ar[A_LD];
-#pragma unroll
-  for (int j = 0; j < A_LD; ++j) {
-    const int k = 4 * (k4b + KSTEP4 * j);
-    ac[j] = k % C;
-    const int rs = k / C;
-    ar[j] = rs / S;
-    as_[j] = rs - ar[j] * S;
-  }
-  const int bn4 = t % BN4, bkr = t / BN4;
-  const int bcol = n0 + 4 * bn4;
-  const bool bcval = bcol < Cop;
-
-  float4 ra[A_LD], rb[B_LD];
-  auto load_one = [&](int i, int k0) {
-    if (i < A_LD) {
-      const int j = i;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int kk = k0 + 4 * (k4b + KSTEP4 * j);
-      if (mval && kk < Ktot) {
-        int hi = hb + ar[j], wi = wb + as_[j];
-        bool ok = true;
-        if (reflect) {
-          hi = reflect_idx(hi, H);
-          wi = reflect_idx(wi, W);
-        } else {
-          ok = (unsigned)hi < (unsigned)H && (unsigned)wi < (unsigned)W;
-        }
-        if (ok) v = *reinterpret_cast<const float4*>(xb + ((long)hi * W + wi) * C + ac[j]);
-      }
-      ra[j] = v;
-    } else {
-      const int j = i - A_LD;
-      const int kr = k0 + bkr + KRSTEP * j;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (bcval && kr < Ktot) v = *reinterpret_cast<const float4*>(wp + (long)kr * Cop + bcol);
-      rb[j] = v;
-    }
-  };
-  auto adv = [&]() {
-#pragma unroll
-    for (int j = 0; j < A_LD; ++j) {
-      ac[j] += BK;
-      while (ac[j] >= C) {
-        ac[j] -= C;
-        if (++as_[j] == S) { as_[j] = 0; ++ar[j]; }
-      }
-    }
-  };
-  auto store = [&](float* As) {
-    float* Bs = As + T::A_ELEMS;
-#pragma unroll
-    for (int j = 0; j < A_LD; ++j) store_a_t<T::LDA>(As, 4 * (k4b + KSTEP4 * j), ml, ra[j]);
-#pragma unroll
-    for (int j = 0; j < B_LD; ++j)
-      *reinterpret_cast<float4*>(Bs + (bkr + KRSTEP * j) * T::LDB + 4 * bn4) = rb[j];
-  };
-
-  f32x16 acc[T::MI][T::NI];
-  zero_acc(acc);
-  main_loop<BM, BN, WM, WN, A_LD + B_LD>(smem, (Ktot + BK - 1) / BK, 0, acc, load_one, adv, store);
-
-  const int wm0 = (wave / T::WAVES_N) * WM, wn0 = (wave % T::WAVES_N) * WN;
-#pragma unroll
-  for (int i = 0; i < T::MI; ++i)
-#pragma unroll
-    for (int j = 0; j < T::NI; ++j) {
-      const int n = n0 + wn0 + 32 * j + (lane & 31);
-      if (n >= Cop) continue;
-      const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int mm = m0 + wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (mm < M) y[(long)mm * Cop + n] = apply_act(acc[i][j][r] + bv, act, slope);
-      }
-    }
-}
-
-// ------------------------------------------------------------------- transposed conv / dgrad
-// out[n][h][w][cx] = sum in[n][ho][wo][cy] * wp[r][s][cy][cx] over h = ho*st - pad + r (zero pad)
-// or, with reflect (st == 1), over reflect(ho + r - pad) == h.
-// blockIdx.z = parity class (a, b): h = a + st*hh; only taps r = r0 + st*i with
-// r0 = (a + pad) mod st contribute, at ho = (h + pad - r) / st (exact).
-constexpr int NOPOS = -(1 << 20);
-
-template <int BM, int BN, int WM, int WN, int ST>
-__global__ __launch_bounds__((Tile<BM, BN, WM, WN>::NT), 2) void conv_tconv_k(
-    const float* __restrict__ in, const float* __restrict__ wp, const float* __restrict__ bias,
-    const float* __restrict__ addend, float* __restrict__ out, int Hi, int Wi, int Cy, int Ho,
-    int Wo, int Cx, int R, int S, int st_rt, int pad, int reflect, int act, float slope, int Nimg) {
-  using T = Tile<BM, BN, WM, WN>;
-  const int st = ST > 0 ? ST : st_rt;  // compile-time stride for the CycleGAN layers (1, 2)
-  constexpr int NT = T::NT;
-  constexpr int KSTEP4 = NT / BM;
-  constexpr int A_LD = BK / 4 / KSTEP4;
-  constexpr int BN4 = BN / 4;
-  constexpr int KRSTEP = NT / BN4;
-  constexpr int B_LD = BK / KRSTEP;
-  __shared__ __attribute__((aligned(16))) float smem[2 * T::STAGE];
-
-  const int ca = blockIdx.z / st, cb = blockIdx.z % st;
-  const int Hc = Ho > ca ? (Ho - ca + st - 1) / st : 0;
-  const int Wc = Wo > cb ? (Wo - cb + st - 1) / st : 0;
-  const int M = Nimg * Hc * Wc;
-  const int mt = remap_mtile(blockIdx.x, gridDim.x);
-  const int m0 = mt * BM, n0 = blockIdx.y * BN;
-  if (m0 >= M) return;
-  const int r0 = (ca + pad) % st, s0 = (cb + pad) % st;
-  const int nr = r0 < R ? (R - r0 + st - 1) / st : 0;
-  const int ns = s0 < S ? (S - s0 + st - 1) / st : 0;
-  const int Ktot = nr * ns * Cy;
-
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int ml = t % BM, k4b = t / BM;
-  const int m = m0 + ml;
-  const bool mval = m < M;
-  // (h + pad) for the direct term and, for reflect, the one mirrored image row/column
-  int hp = 0, wq = 0, hm = NOPOS, wmr = NOPOS;
-  const float* ib = in;
-  if (mval) {
-    const int hw = Hc * Wc;
-    const int n = m / hw, rem = m - n * hw, hh = rem / Wc, ww = rem - hh * Wc;
-    const int h = ca + st * hh, w = cb + st * ww;
-    hp = h + pad;
-    wq = w + pad;
-    if (reflect) {
-      if (h >= 1 && h <= pad) hm = pad - h;
-      else if (h >= Ho - 1 - pad && h <= Ho - 2) hm = 2 * Ho - 2 - h + pad;
-      if (w >= 1 && w <= pad) wmr = pad - w;
-      else if (w >= Wo - 1 - pad && w <= Wo - 2) wmr = 2 * Wo - 2 - w + pad;
-    }
-    ib = in + (long)n * Hi * Wi * Cy;
-  }
-  int ac[A_LD], ais[A_LD], air[A_LD];
-#pragma unroll
-  for (int j = 0; j < A_LD; ++j) {
-    const int k = 4 * (k4b + KSTEP4 * j);
-    ac[j] = k % Cy;
-    const int tp = k / Cy;
-    air[j] = ns > 0 ? tp / ns : 0;
-    ais[j] = tp - air[j] * ns;
-  }
-  const int bn4 = t % BN4, bkr = t / BN4;
-  const int bcol = n0 + 4 * bn4;
-  const bool bcval = bcol < Cx;
-  int bc[B_LD], bis[B_LD], bir[B_LD];
-#pragma unroll
-  for (int j = 0; j < B_LD; ++j) {
-    const int k = bkr + KRSTEP * j;
-    bc[j] = k % Cy;
-    const int tp = k / Cy;
-    bir[j] = ns > 0 ? tp / ns : 0;
-    bis[j] = tp - bir[j] * ns;
-  }
-
-  float4 ra[A_LD], rb[B_LD];
-  auto gather1 = [&](int hpos, int wpos, int r, int s, int c, float4& v) {
-    const int dh = hpos - r, dw = wpos - s;
-    if (dh >= 0 && dw >= 0) {
-      const int ho = dh / st, wo = dw / st;
-      if (ho < Hi && wo < Wi)
-        add4(v, *reinterpret_cast<const float4*>(ib + ((long)ho * Wi + wo) * Cy + c));
-    }
-  };
-  auto load_one = [&](int i, int k0) {
-    if (i < A_LD) {
-      const int j = i;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int kk = k0 + 4 * (k4b + KSTEP4 * j);
-      if (mval && kk < Ktot) {
-        const int r = r0 + st * air[j], s = s0 + st * ais[j];
-        gather1(hp, wq, r, s, ac[j], v);
-        if (hm != NOPOS) gather1(hm, wq, r, s, ac[j], v);
-        if (wmr != NOPOS) {
-          gather1(hp, wmr, r, s, ac[j], v);
-          if (hm != NOPOS) gather1(hm, wmr, r, s, ac[j], v);
-        }
-      }
-      ra[j] = v;
-    } else {
-      const int j = i - A_LD;
-      const int kk = k0 + bkr + KRSTEP * j;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (bcval && kk < Ktot) {
-        const int row = ((r0 + st * bir[j]) * S + (s0 + st * bis[j])) * Cy + bc[j];
-        v = *reinterpret_cast<const float4*>(wp + (long)row * Cx + bcol);
-      }
-      rb[j] = v;
-    }
-  };
-  auto adv = [&]() {
-#pragma unroll
-    for (int j = 0; j < A_LD; ++j) {
-      ac[j] += BK;
-      while (ac[j] >= Cy) {
-        ac[j] -= Cy;
-        if (++ais[j] == ns) { ais[j] = 0; ++air[j]; }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < B_LD; ++j) {
-      bc[j] += BK;
-      while (bc[j] >= Cy) {
-        bc[j] -= Cy;
-        if (++bis[j] == ns) { bis[j] = 0; ++bir[j]; }
-      }
-    }
-  };
-  auto store = [&](float* As) {
-    float* Bs = As + T::A_ELEMS;
-#pragma unroll
-    for (int j = 0; j < A_LD; ++j) store_a_t<T::LDA>(As, 4 * (k4b + KSTEP4 * j), ml, ra[j]);
-#pragma unroll
-    for (int j = 0; j < B_LD; ++j)
-      *reinterpret_cast<float4*>(Bs + (bkr + KRSTEP * j) * T::LDB + 4 * bn4) = rb[j];
-  };
-
-  f32x16 acc[T::MI][T::NI];
-  zero_acc(acc);
-  main_loop<BM, BN, WM, WN, A_LD + B_LD>(smem, (Ktot + BK - 1) / BK, 0, acc, load_one, adv, store);
-
-  const int wm0 = (wave / T::WAVES_N) * WM, wn0 = (wave % T::WAVES_N) * WN;
-  const int hw = Hc * Wc;
-#pragma unroll
-  for (int i = 0; i < T::MI; ++i)
-#pragma unroll
-    for (int j = 0; j < T::NI; ++j) {
-      const int n = n0 + wn0 + 32 * j + (lane & 31);
-      if (n >= Cx) continue;
-      const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int mm = m0 + wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (mm >= M) continue;
-        const int nimg = mm / hw, rem = mm - nimg * hw, hh = rem / Wc, ww = rem - hh * Wc;
-        const long o = (((long)nimg * Ho + (ca + st * hh)) * Wo + (cb + st * ww)) * Cx + n;
-        float v = apply_act(acc[i][j][r] + bv, act, slope);
-        if (addend) v += addend[o];
-        out[o] = v;
-      }
-    }
 }
 
 // ------------------------------------------------------------------------------------------ wgrad
@@ -696,16 +397,6 @@ static int tile_bn(TileKind k) {
   return k == T128x64 || k == T64x64 ? 64 : (k == T256x32 ? 32 : 128);
 }
 
-static TileKind pick_tile(long M, int Nc, int which) {
-  if (g_tile_override[which] != TAUTO) return (TileKind)g_tile_override[which];
-  if (Nc <= 32) return T256x32;
-  if (Nc <= 64) return M / 128 >= 256 ? T128x64 : T64x64;
-  const long n128 = (Nc + 127) / 128;
-  if ((M / 128) * n128 >= 200) return T128x128w8;
-  if ((M / 64) * n128 >= 200) return T64x128;
-  return T64x64;
-}
-
 #define VST_DISPATCH_TILE(kind, LAUNCH)                       \
   switch (kind) {                                              \
     case T128x128w8: LAUNCH(128, 128, 64, 32); break;          \
@@ -750,8 +441,6 @@ static int pick_splits(int tiles, int slots, int max_ns, int min_ns = 1) {
   return ns;
 }
 
-static constexpr int g_wg_kind_s2 = -1;
-
 static WgradPlan plan_wgrad(int N, int H, int W, int Ho, int Wo, int Cx, int Cyp, int R, int S,
                             int stride, int math) {
   constexpr int RK_WIDE_KIND = 5;  // rk tile kind of the wide (Cyp > 64, Mw >= 1024) x3 weight gradients
@@ -783,7 +472,6 @@ static WgradPlan plan_wgrad(int N, int H, int W, int Ho, int Wo, int Cx, int Cyp
     // 576 rows = 2.25 x 256, 1152 = 4.5 x 256) run on 128x128 tiles of 8 waves (64x32); round-5 sweep
     // (profiles/r05e_convT_wgrad_tiles.jsonl): 178 -> 172 / 149 -> 136 us at N = 8
     if (kind == 7 && ceil_div(p.Mw, 256) * 256 > ceil_div(p.Mw, 128) * 128) kind = 0;
-    if (g_wg_kind_s2 >= 0 && stride == 2) kind = g_wg_kind_s2;  // developer A/B (g_wg_kind_s2)
     p.tile = (TileKind)kind;
     int bm, bn, bk, slots;
     bf_wgrad_geom(kind, math, &bm, &bn, &bk, &slots);
@@ -846,14 +534,6 @@ static WgradPlan plan_wgrad(int N, int H, int W, int Ho, int Wo, int Cx, int Cyp
 
 using namespace vst;
 
-// 4-channel inputs (images) on the split-bf16 kernels (conv_fprop_bf_k<.., false, 3>) rather than
-// the fp32 [row][k] kernels; g_bf_c4 = false restores the latter (route selectors like this are compile-time constants).
-// wgrad_reduce_store_k on 16-row blocks (g_wg_red16 = false: 32-row): twice the blocks for the same slabs,
-// -0.16 ms/step in the same-box A/B (profiles/r03d_wgred_step_ab.jsonl)
-static constexpr bool g_wg_red16 = true;
-
-static constexpr bool g_bf_c4 = true;
-
 extern "C" void vst_debug_set_tiles(int fprop, int tconv, int wgrad) {
   g_tile_override[0] = fprop;
   g_tile_override[1] = tconv;
@@ -870,10 +550,11 @@ extern "C" int vst_conv_plan_fwd(int N, int H, int W, int Cx, int Cop, int R, in
   *tail_kind = -1;
   if (Cop == 4) {
     *kind = VST_PLAN_SKINNY;
-  } else if (Cx == 4 && g_bf_c4 && g_tile_override[0] < 0 && padh == padw &&
+  } else if (Cx == 4 && g_tile_override[0] < 0 && padh == padw &&
              c4_direct_ok(Cx, Cop, R, S, stride, Ho, Wo, math)) {
     *kind = VST_PLAN_C4_DIRECT;
-  } else if (math != VST_MATH_F32 && (Cx % 8 == 0 || (Cx == 4 && g_bf_c4))) {
+  } else if (math != VST_MATH_F32 && (Cx % 8 == 0 || Cx == 4)) {
+    // (4-channel inputs, the images, too: conv_fprop_bf_k<.., false, 3> rather than the fp32 [row][k] kernels)
     bf_plan((long)N * Ho * Wo, Cop, math, g_tile_override[0], kind, m_split, tail_kind);
   } else {
     *kind = VST_PLAN_RK;
@@ -883,9 +564,8 @@ extern "C" int vst_conv_plan_fwd(int N, int H, int W, int Cx, int Cop, int R, in
 
 static int conv_fwd_impl(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
                          int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int padh, int padw,
-                         int pad_mode, int act, float slope, int math, hipStream_t s, double* part = nullptr,
-                         int* nsplit = nullptr, float* tws = nullptr, size_t tws_bytes = 0, int co_real = 4) {
-  if (nsplit) *nsplit = 0;
+                         int pad_mode, int act, float slope, int math, hipStream_t s, double* part, int* nsplit,
+                         float* tws, size_t tws_bytes, int co_real) {
   VST_REQUIRE(x && wp && y, "conv2d_fwd: null pointer");
   VST_REQUIRE(math >= VST_MATH_F32 && math <= VST_MATH_BF16X6, "conv2d_fwd: bad math %d", math);
   VST_REQUIRE(N > 0 && H > 0 && W > 0 && R > 0 && S > 0 && stride > 0 && padh >= 0 && padw >= 0,
@@ -900,7 +580,7 @@ static int conv_fwd_impl(const float* x, const float* wp, const void* wsplit, co
     return skinny_out_launch(0, x, wp, bias, nullptr, y, N, H, W, Cx, Ho, Wo, R, S, stride, padh, refl,
                              act, slope, s, co_real);
   }
-  if (math != VST_MATH_F32 && wsplit && (Cx % 8 == 0 || (Cx == 4 && g_bf_c4))) {
+  if (math != VST_MATH_F32 && wsplit && (Cx % 8 == 0 || Cx == 4)) {
     // InstanceNorm partials from the epilogue: 32-pixel groups, so the image size must divide
     const bool stats = part && nsplit && (Ho * Wo) % 32 == 0;
     const int rc = bf_fprop_launch(x, wsplit, (long)Cop * R * S * Cx, bias, y, N, H, W, Cx, Ho, Wo, Cop, R, S,
@@ -914,74 +594,58 @@ static int conv_fwd_impl(const float* x, const float* wp, const void* wsplit, co
   return check_launch("conv2d_fwd");
 }
 
-extern "C" int vst_conv2d_fwd(const float* x, const float* wp, const void* wsplit, const float* bias,
-                              float* y, int N,
-                              int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
-                              int pad_mode, int act, float slope, int math, void* stream) {
-  return conv_fwd_impl(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad, pad, pad_mode, act, slope,
-                       math, (hipStream_t)stream);
-}
-
-extern "C" int vst_conv2d_fwd_co(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
-                                 int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad, int pad_mode,
-                                 int act, float slope, int math, int co_real, void* stream) {
-  VST_REQUIRE(co_real >= 1 && co_real <= Cop, "conv2d_fwd_co: bad real channel count %d", co_real);
-  return conv_fwd_impl(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad, pad, pad_mode, act, slope,
-                       math, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, co_real);
-}
-
-extern "C" size_t vst_conv2d_fwd_co_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
-                                             int pad_mode, int co_real) {
-  if (N <= 0 || H <= 0 || W <= 0 || co_real != 1 || Cop != 4 || !g_head) return 0;
-  const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
+// The head's tap-GEMM workspace (the PatchGAN head: one real channel of 4, patch.hip), 0 for any other conv
+static size_t head_tap_ws_bytes(int N, int H, int W, int Cx, int R, int S, int stride, int pad_h, int pad_w,
+                                int pad_mode, int co_real) {
+  if (N <= 0 || H <= 0 || W <= 0 || R <= 0 || S <= 0 || stride <= 0 || co_real != 1 || pad_h != pad_w) return 0;
+  const int Ho = (H + 2 * pad_h - R) / stride + 1, Wo = (W + 2 * pad_w - S) / stride + 1;
   if (Ho <= 0 || Wo <= 0 || !head_ok(Cx, R, S, stride, pad_mode == VST_PAD_REFLECT, Wo) || !head_tap_ok(Cx)) return 0;
   return head_tap_ws_floats(N, H, W) * sizeof(float);
 }
 
-extern "C" int vst_conv2d_fwd_co_ws(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
-                                    int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
-                                    int pad_mode, int act, float slope, int math, int co_real, float* ws,
-                                    size_t ws_bytes, void* stream) {
-  const size_t need = vst_conv2d_fwd_co_ws_bytes(N, H, W, Cx, Cop, R, S, stride, pad, pad_mode, co_real);
-  if (need && ws && ws_bytes >= need && x && wp && y) {
-    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
-    return head_tap_fwd_launch(x, wp, bias, y, ws, N, H, W, Cx, Ho, Wo, R, S, pad, act, slope, (hipStream_t)stream);
-  }
-  return vst_conv2d_fwd_co(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad, pad_mode, act, slope, math,
-                           co_real, stream);
-}
-
-extern "C" int vst_conv2d_fwd_in(const float* x, const float* wp, const void* wsplit, const float* bias,
-                                 float* y, int N, int H, int W, int Cx, int Cop, int R, int S, int stride,
-                                 int pad, int pad_mode, int act, float slope, int math, double* part,
-                                 int* nsplit, void* stream) {
-  VST_REQUIRE(part && nsplit, "conv2d_fwd_in: null partials");
-  return conv_fwd_impl(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad, pad, pad_mode, act, slope,
-                       math, (hipStream_t)stream, part, nsplit);
-}
-
-extern "C" size_t vst_conv2d_fwd_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
-                                          int math) {
-  if (N <= 0 || H <= 0 || W <= 0 || R <= 0 || S <= 0 || stride <= 0 || Cx % 8 || Cop == 4) return 0;
-  const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
+// Cop == 4: the head's tap-GEMM workspace; any other Cop: the split-K slabs of the x6 plans (never both)
+extern "C" size_t vst_conv2d_fwd_ex_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h,
+                                             int pad_w, int pad_mode, int math, int co_real) {
+  if (Cop == 4) return head_tap_ws_bytes(N, H, W, Cx, R, S, stride, pad_h, pad_w, pad_mode, co_real);
+  if (N <= 0 || H <= 0 || W <= 0 || R <= 0 || S <= 0 || stride <= 0 || Cx % 8) return 0;
+  const int Ho = (H + 2 * pad_h - R) / stride + 1, Wo = (W + 2 * pad_w - S) / stride + 1;
   if (Ho <= 0 || Wo <= 0 || g_tile_override[0] >= 0) return 0;
   return bf_fprop_ws_floats((long)N * Ho * Wo, Cop, Cx, R, S, math) * sizeof(float);
 }
 
-extern "C" int vst_conv2d_fwd_ws(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
-                                 int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad, int pad_mode,
-                                 int act, float slope, int math, double* part, int* nsplit, float* ws,
-                                 size_t ws_bytes, void* stream) {
-  return conv_fwd_impl(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad, pad, pad_mode, act, slope,
-                       math, (hipStream_t)stream, part, nsplit, ws, ws_bytes);
+extern "C" int vst_conv2d_fwd_ex(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
+                                 int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h, int pad_w,
+                                 int pad_mode, int act, float slope, int math, int co_real, double* part, int* nsplit,
+                                 float* ws, size_t ws_bytes, void* stream) {
+  if (nsplit) *nsplit = 0;
+  VST_REQUIRE(co_real >= 1 && co_real <= Cop, "conv2d_fwd_ex: bad real channel count %d", co_real);
+  VST_REQUIRE(!part == !nsplit, "conv2d_fwd_ex: part and nsplit go together");
+  if (Cop == 4 && ws && x && wp && y) {
+    const size_t need = head_tap_ws_bytes(N, H, W, Cx, R, S, stride, pad_h, pad_w, pad_mode, co_real);
+    if (need && ws_bytes >= need) {
+      const int Ho = (H + 2 * pad_h - R) / stride + 1, Wo = (W + 2 * pad_w - S) / stride + 1;
+      return head_tap_fwd_launch(x, wp, bias, y, ws, N, H, W, Cx, Ho, Wo, R, S, pad_h, act, slope,
+                                 (hipStream_t)stream);
+    }
+  }
+  return conv_fwd_impl(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad_h, pad_w, pad_mode, act, slope,
+                       math, (hipStream_t)stream, part, nsplit, ws, ws_bytes, co_real);
+}
+
+extern "C" int vst_conv2d_fwd(const float* x, const float* wp, const void* wsplit, const float* bias,
+                              float* y, int N,
+                              int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
+                              int pad_mode, int act, float slope, int math, void* stream) {
+  return vst_conv2d_fwd_ex(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad, pad, pad_mode, act, slope,
+                           math, Cop, nullptr, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int vst_conv_plan_fwd_tail(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
                                       int math, int* ksplit) {
   VST_REQUIRE(ksplit, "conv_plan_fwd_tail: null");
   *ksplit = 0;
-  const size_t b = vst_conv2d_fwd_ws_bytes(N, H, W, Cx, Cop, R, S, stride, pad, math);
-  if (b) {
+  // (co_real = Cop: the split-K slabs, never the head's workspace)
+  if (vst_conv2d_fwd_ex_ws_bytes(N, H, W, Cx, Cop, R, S, stride, pad, pad, VST_PAD_ZERO, math, Cop)) {
     const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
     int mf;
     bf_split_plan((long)N * Ho * Wo, Cop, Cx, R, S, math, -1, &mf, ksplit);
@@ -989,41 +653,8 @@ extern "C" int vst_conv_plan_fwd_tail(int N, int H, int W, int Cx, int Cop, int 
   return VST_OK;
 }
 
-// vst_conv2d_fwd_hw with a padding mode (vst_tapconv_h_fwd's R x 1 reflect conv)
-extern "C" int vst_conv2d_fwd_hwp(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
-                                  int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h, int pad_w,
-                                  int pad_mode, int act, float slope, int math, void* stream) {
-  return conv_fwd_impl(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad_h, pad_w, pad_mode, act, slope,
-                       math, (hipStream_t)stream);
-}
-
-extern "C" int vst_conv2d_fwd_hw(const float* x, const float* wp, const void* wsplit, const float* bias,
-                                 float* y, int N, int H, int W, int Cx, int Cop, int R, int S, int stride,
-                                 int pad_h, int pad_w, int act, float slope, int math, void* stream) {
-  return conv_fwd_impl(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad_h, pad_w, VST_PAD_ZERO, act,
-                       slope, math, (hipStream_t)stream);
-}
-
-// vst_conv2d_fwd_hw with a workspace: the split-K plans of vst_conv2d_fwd_ws for grids that cannot fill the CUs
-// (RAFT's SepConvGRU (1,5) / (5,1) convs at 1/8 resolution: M = 7040 rows at Sintel size)
-extern "C" size_t vst_conv2d_fwd_hw_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h,
-                                             int pad_w, int math) {
-  if (N <= 0 || H <= 0 || W <= 0 || R <= 0 || S <= 0 || stride <= 0 || Cx % 8 || Cop == 4) return 0;
-  const int Ho = (H + 2 * pad_h - R) / stride + 1, Wo = (W + 2 * pad_w - S) / stride + 1;
-  if (Ho <= 0 || Wo <= 0 || g_tile_override[0] >= 0) return 0;
-  return bf_fprop_ws_floats((long)N * Ho * Wo, Cop, Cx, R, S, math) * sizeof(float);
-}
-
-extern "C" int vst_conv2d_fwd_hw_ws(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
-                                    int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h,
-                                    int pad_w, int act, float slope, int math, float* ws, size_t ws_bytes,
-                                    void* stream) {
-  return conv_fwd_impl(x, wp, wsplit, bias, y, N, H, W, Cx, Cop, R, S, stride, pad_h, pad_w, VST_PAD_ZERO, act,
-                       slope, math, (hipStream_t)stream, nullptr, nullptr, ws, ws_bytes);
-}
-
 // One phase (a, b) of a stride-2 ConvTranspose2d(k3, p1, op1) stored straight into the interleaved
-// 2H x 2W output y (the phase conv of conv2d_fwd_hw(x, wp, R = 1 + a, S = 1 + b, pad a / b), whose pixel
+// 2H x 2W output y (the phase conv of ops.conv2d_fwd_hw(x, wp, R = 1 + a, S = 1 + b, pad a / b), whose pixel
 // (ph, pw) is y's (2(ph-a)+a, 2(pw-b)+b)): the four phases replace four phase images + the
 // vst_interleave_phases pass.  Split-bf16 arithmetic only (VST_EUNSUPPORTED otherwise: use the
 // phase images + interleave).
@@ -1083,25 +714,11 @@ extern "C" int vst_conv2d_tfwd(const float* in, const float* wp, const float* bi
   VST_REQUIRE(!refl || (stride == 1 && Ho > 2 * pad + 1 && Wo > 2 * pad + 1),
               "conv2d_tfwd: reflect needs stride 1 and H, W > 2*pad+1");
   hipStream_t s = (hipStream_t)stream;
-  const int Hc = (Ho + stride - 1) / stride, Wc = (Wo + stride - 1) / stride;
-  const int Mmax = N * Hc * Wc;
   if (tfwd_plan(Cx) == VST_PLAN_SKINNY)  // image-channel data gradients: VALU path (skinny.hip)
     return skinny_out_launch(1, in, wp, bias, addend, out, N, Hi, Wi, Cy, Ho, Wo, R, S, stride, pad,
                              refl, act, slope, s);
-#define VST_TCONV_ST(BM_, BN_, WM_, WN_, ST_)                                                      \
-  hipLaunchKernelGGL((conv_tconv_k<BM_, BN_, WM_, WN_, ST_>),                                       \
-                     dim3(ceil_div(Mmax, BM_), ceil_div(Cx, BN_), stride * stride),                  \
-                     dim3(Tile<BM_, BN_, WM_, WN_>::NT), 0, s, in, wp, bias, addend, out, Hi, Wi, Cy, \
-                     Ho, Wo, Cx, R, S, stride, pad, refl, act, slope, N)
-#define VST_TCONV(BM_, BN_, WM_, WN_)                     \
-  if (stride == 1) VST_TCONV_ST(BM_, BN_, WM_, WN_, 1);     \
-  else if (stride == 2) VST_TCONV_ST(BM_, BN_, WM_, WN_, 2); \
-  else VST_TCONV_ST(BM_, BN_, WM_, WN_, 0);
-  (void)Mmax;
   rk_tconv_launch(in, wp, bias, addend, out, N, Hi, Wi, Cy, Ho, Wo, Cx, R, S, stride, pad, refl, act,
                   slope, g_tile_override[1], math, s);
-#undef VST_TCONV
-#undef VST_TCONV_ST
   return check_launch("conv2d_tfwd");
 }
 
@@ -1110,7 +727,7 @@ extern "C" int vst_conv2d_tfwd_co(const float* in, const float* wp, const float*
                                   int pad, int pad_mode, int act, float slope, int math, int co_real, void* stream) {
   VST_REQUIRE(co_real >= 1 && co_real <= Cy, "conv2d_tfwd_co: bad real channel count %d", co_real);
   const int refl = pad_mode == VST_PAD_REFLECT;
-  if (in && wp && out && co_real == 1 && Cy == 4 && !bias && act == VST_ACT_NONE && g_head && N > 0 && Hi > 0 &&
+  if (in && wp && out && co_real == 1 && Cy == 4 && !bias && act == VST_ACT_NONE && N > 0 && Hi > 0 &&
       Wi > 0 && pad >= 0 && head_ok(Cx, R, S, stride, refl, Wi) && Ho == Hi + R - 1 - 2 * pad &&
       Wo == Wi + S - 1 - 2 * pad)
     return head_dgrad_launch(in, wp, addend, out, N, Hi, Wi, Cx, Ho, Wo, R, S, pad, (hipStream_t)stream);
@@ -1123,15 +740,13 @@ extern "C" int vst_conv2d_tfwd_co(const float* in, const float* wp, const float*
 static constexpr int WG_GROUP = 16;
 // Image-input layers (x NHWC4 holding 3 logical channels) on the split-bf16 kernel: the GEMM takes only
 // the rows (tap, ci < 3) of the 4-plane x image — M = 3RS instead of 4RS (the generator's first 7x7
-// conv: 147 rows = 3 tiles of 64 instead of 4).  g_wg_c3 = false: all four planes.
-static constexpr bool g_wg_c3 = true;
-
+// conv: 147 rows = 3 tiles of 64 instead of 4).
 // The GEMM's plan for (Cx, logical Ci): p planned with Cx = 3 when the rule above applies; its
 // operand-copy sizes stay those of the Cx-channel images.
 static WgradPlan plan_wgrad_gemm(const WgradPlan& p, int N, int H, int W, int Ho, int Wo, int Cx, int Ci, int Cyp,
                                  int R, int S, int stride, int math, int* Cxg) {
   *Cxg = Cx;
-  if (!(g_wg_c3 && p.bfk && Cx == 4 && Ci == 3)) return p;
+  if (!(p.bfk && Cx == 4 && Ci == 3)) return p;
   WgradPlan q = plan_wgrad(N, H, W, Ho, Wo, 3, Cyp, R, S, stride, math);
   if (!q.bfk || q.wpad != p.wpad || q.pad != p.pad) return p;
   q.xt_floats = p.xt_floats;
@@ -1184,11 +799,11 @@ extern "C" int vst_conv_plan_tfwd(int Cx, int* plan) {
 extern "C" int vst_tap64_ok(int Cx, int R, int W, int math) { return tap64_ok(Cx, R, W, math) ? 1 : 0; }
 
 extern "C" int vst_head_ok(int Cin, int R, int S, int stride, int pad_mode, int Wo) {
-  return g_head && head_ok(Cin, R, S, stride, pad_mode == VST_PAD_REFLECT, Wo) ? 1 : 0;
+  return head_ok(Cin, R, S, stride, pad_mode == VST_PAD_REFLECT, Wo) ? 1 : 0;
 }
 
 extern "C" int vst_img_wgrad_ok(int Cx, int Cyp, int R, int S, int stride, int pad_mode, int Ci, int Wo) {
-  return g_img_wgrad && img_wgrad_ok(Cx, Cyp, R, S, stride, pad_mode == VST_PAD_REFLECT, Ci, Wo) ? 1 : 0;
+  return img_wgrad_ok(Cx, Cyp, R, S, stride, pad_mode == VST_PAD_REFLECT, Ci, Wo) ? 1 : 0;
 }
 
 extern "C" int vst_skinny_split_ok(int N, int Ho, int Wo, int Cx, int R, int S) {
@@ -1246,11 +861,11 @@ extern "C" int vst_conv2d_wgrad_pre(const float* x, const float* x_t, const floa
               "conv2d_wgrad: channel strides must be multiples of 4");
   VST_REQUIRE(Co <= Cyp && Ci <= Cx, "conv2d_wgrad: logical channels exceed strides");
   VST_REQUIRE(pad_mode == VST_PAD_ZERO || (pad < H && pad < W), "conv2d_wgrad: reflect pad >= size");
-  if (!x_t && !dy_planes && g_img_wgrad && img_wgrad_ok(Cx, Cyp, R, S, stride, pad_mode == VST_PAD_REFLECT, Ci, Wo) &&
+  if (!x_t && !dy_planes && img_wgrad_ok(Cx, Cyp, R, S, stride, pad_mode == VST_PAD_REFLECT, Ci, Wo) &&
       Co <= Cyp && ws_bytes >= img_wgrad_ws_floats(N, Ho, Wo) * sizeof(float))
     return img_wgrad_launch(x, dy, dw, nullptr, ws, N, H, W, Ho, Wo, Cyp, R, S, stride, pad, Co, Ci, so, si, accumulate,
                             (hipStream_t)stream);
-  int Cxg;  // the GEMM's channel count (3 for image-input layers, g_wg_c3)
+  int Cxg;  // the GEMM's channel count (3 for image-input layers)
   const WgradPlan p = plan_wgrad_gemm(p0, N, H, W, Ho, Wo, Cx, Ci, Cyp, R, S, stride, math, &Cxg);
   VST_REQUIRE(ws_bytes >= wgrad_ws_floats(p, Cyp) * sizeof(float),
               "conv2d_wgrad: workspace too small (%zu bytes)", ws_bytes);
@@ -1287,7 +902,7 @@ extern "C" int vst_conv2d_wgrad_pre(const float* x, const float* x_t, const floa
       rk_wgrad_launch(xt, dyt, ws, N, H, W, Cx, Ho, Wo, Cyp, S, pad, stride, p.Mw, p.chunk, p.nsplit,
                       (int)p.tile, math, s);
     }
-  } else if (Cyp == 4 && Co == 1 && g_head && head_ok(Cx, R, S, stride, refl, Wo) &&
+  } else if (Cyp == 4 && Co == 1 && head_ok(Cx, R, S, stride, refl, Wo) &&
              ws_bytes >= head_wgrad_ws_floats(N, H, Cx, R, S) * sizeof(float)) {
     // the PatchGAN head: the activation read once, partials reduced in a fixed order straight into dw
     return head_wgrad_launch(x, dy, dw, ws, N, H, W, Cx, Ci, Ho, Wo, R, S, pad, si, accumulate, s);
@@ -1313,10 +928,11 @@ extern "C" int vst_conv2d_wgrad_pre(const float* x, const float* x_t, const floa
                        p.nsplit, WG_GROUP);
     red = l2;
   }
-  // 16-row blocks: twice the blocks (the 2304 x 256 ResnetBlock gradient: 288 -> 576); with at most 2 slabs the pass is
+  // 16-row blocks: twice the blocks for the same slabs (the 2304 x 256 ResnetBlock gradient: 288 -> 576; -0.16 ms/step
+  // against 32-row blocks in the same-box A/B, profiles/r03d_wgred_step_ab.jsonl); with at most 2 slabs the pass is
   // a transpose whose stores / accumulate reads are 16 floats per channel row with 16-row blocks: 32-row blocks keep
   // them whole 128-B lines (the StarGAN discriminator's 1024 -> 2048 layer, one slab, accumulated: 134 MB)
-  if (g_wg_red16 && nred > 2)
+  if (nred > 2)
     hipLaunchKernelGGL(wgrad_reduce_store_k<1>, dim3(ceil_div(Ci * R * S, 16), ceil_div(Co, 64)), dim3(256), 0, s,
                        red, dw, Cxg, Cyp, R * S, Co, Ci, so, si, accumulate, nred, slab);
   else
@@ -1548,10 +1164,10 @@ extern "C" int vst_conv2d_wgrad_bias(const float* x, const float* dy, float* dw,
               "conv2d_wgrad_bias: bad args");
   const int refl = pad_mode == VST_PAD_REFLECT;
   hipStream_t s = (hipStream_t)stream;
-  if (g_img_wgrad && img_wgrad_ok(Cx, Cyp, R, S, stride, refl, Ci, Wo) &&
+  if (img_wgrad_ok(Cx, Cyp, R, S, stride, refl, Ci, Wo) &&
       ws_bytes >= img_wgrad_ws_floats(N, Ho, Wo) * sizeof(float))
     return img_wgrad_launch(x, dy, dw, db, ws, N, H, W, Ho, Wo, Cyp, R, S, stride, pad, Co, Ci, so, si, accumulate, s);
-  if (Cyp == 4 && Co == 1 && g_head && head_ok(Cx, R, S, stride, refl, Wo) &&
+  if (Cyp == 4 && Co == 1 && head_ok(Cx, R, S, stride, refl, Wo) &&
       ws_bytes >= head_wgrad_ws_floats(N, H, Cx, R, S) * sizeof(float))
     return head_wgrad_launch(x, dy, dw, ws, N, H, W, Cx, Ci, Ho, Wo, R, S, pad, si, accumulate, s, db);
   ::vst::set_error("conv2d_wgrad_bias: no fused route for this shape (use vst_conv2d_wgrad + vst_channel_sum)");

@@ -1091,7 +1091,7 @@ __device__ __forceinline__ void conv_fprop_bf_body(
         s2 += (double)v * v;
       }
       if (part) {
-        // InstanceNorm statistics partials of this 32-row group (vst_conv2d_fwd_in): lanes l and
+        // InstanceNorm statistics partials of this 32-row group (part / nsplit of vst_conv2d_fwd_ex): lanes l and
         // l ^ 32 hold the group's two row halves of column n; fixed order, fp64.  The launcher
         // guarantees Ho*Wo % 32 == 0, so a group never straddles an image or M.
         s1 += __shfl_xor(s1, 32);

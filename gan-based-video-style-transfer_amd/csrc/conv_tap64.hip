@@ -246,7 +246,6 @@ __global__ __launch_bounds__(NT, 1) void tap64_k(const float* __restrict__ x, co
 
 }  // namespace tap64
 
-static constexpr bool g_tap64 = true;
 // 1024-wide rows as column segments: groups of 4 rows x 256 z columns (250 output columns + the taps' 6-column halo)
 // instead of one whole row per group — a row's K-steps each split a new input row for only one output row
 // (RI = 1), 4x the operand-split VALU per MFMA of the 4-row groups (the C3 / Sintel-size last layer and the
@@ -256,7 +255,7 @@ static constexpr bool g_tap64 = true;
 // math, W in {256, 512, 1024} (a group is 1024 / W whole rows, or 4 rows of a 1024-wide row's column segment),
 // reflect 'same' or zero padding.
 bool tap64_ok(int Cx, int R, int W, int math) {
-  return g_tap64 && Cx == tap64::CI && R == tap64::R && W % 256 == 0 && tap64::GQ % W == 0 &&
+  return Cx == tap64::CI && R == tap64::R && W % 256 == 0 && tap64::GQ % W == 0 &&
          (math == VST_MATH_BF16X6 || math == VST_MATH_BF16X3);
 }
 

@@ -203,9 +203,8 @@ __device__ __forceinline__ bool fold_slices(const double* __restrict__ part, int
 // Channels per finalize block: 16, or 4 when (C / 16) x N blocks would leave most CUs idle over many
 // slices (the first conv's 64 channels x 8 images over 2048 slices: 32 blocks, 14 us; B=1 inference's
 // 256 channels: 16 blocks) — 4x the blocks, each thread's slice chain 4x shorter.
-static constexpr bool g_fin_narrow = true;
 static int fin_cpb(int C, int N, int nsplit) {
-  return (!g_fin_narrow || (long)((C + 15) / 16) * N >= 128 || nsplit < 64) ? 16 : 4;
+  return ((long)((C + 15) / 16) * N >= 128 || nsplit < 64) ? 16 : 4;
 }
 
 // grid (C/CPB, N), 256 threads

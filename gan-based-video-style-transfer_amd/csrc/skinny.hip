@@ -11,7 +11,8 @@
 //   skinny_out_k   out[p][0..3] = act(bias + sum_{tap, c} in[gather(p, tap)][c] * w[tap][c][0..3])
 //                  MODE 0: forward conv gather (stride, zero/reflect pad);
 //                  MODE 1: transposed-conv / data-gradient gather (per parity class in blockIdx.z,
-//                          reflect mirrors for stride 1) — the same index rules as conv_tconv_k.
+//                          reflect mirrors for stride 1) — the same index rules as conv_tconv_rk_k
+//                          (conv_rk.hip).
 //                  One output pixel per KS consecutive lanes: the KS lanes split the channel loop
 //                  (K-split for the 30x30 PatchGAN head, KS = 1 for the 256x256 image layers) and
 //                  are combined with wave shuffles.  Weights are wave-uniform (scalar loads); the
@@ -277,15 +278,10 @@ __global__ __launch_bounds__(256) void skinny_wgrad_k(
     *reinterpret_cast<float4*>(sl + 4 * a) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
 }
 
-// few-pixel long-K forwards on the split kernel (skinny_split_k); g_skinny_split = false: the per-pixel kernel
-static constexpr bool g_skinny_split = true;
-
-// the PatchGAN head's one-channel forward on its row kernel (patch.hip); g_head = false: the per-pixel gather here
-const bool g_head = true;
-
-// Does a forward (mode 0) over `pix` output pixels take skinny_split_k, and with which channel chunk / split count?
+// Does a forward (mode 0) over `pix` output pixels take skinny_split_k (few pixels, long K), and with which channel
+// chunk / split count?
 bool skinny_split_plan(int mode, long pix, int R, int S, int Cin, int* CC_out, int* nsplit_out) {
-  if (!(mode == 0 && g_skinny_split && pix * 16 <= 4096 && (long)R * S * Cin >= 4096 && Cin % 64 == 0)) return false;
+  if (!(mode == 0 && pix * 16 <= 4096 && (long)R * S * Cin >= 4096 && Cin % 64 == 0)) return false;
   int CC = Cin;
   while (CC > 256 && CC % 2 == 0 && (CC / 2) % 64 == 0) CC /= 2;
   const int nsplit = R * S * (Cin / CC);
@@ -317,7 +313,8 @@ int skinny_out_launch(int mode, const float* in, const float* wp, const float* b
     case 8: VST_SK(M_, ST_, 8); break;          \
     default: VST_SK(M_, ST_, 16); break;        \
   }
-  if (mode == 0 && co_real == 1 && g_head && head_ok(Cin, R, S, st, reflect, Wo) && !addend)
+  // the PatchGAN head's one-channel forward: its row kernel (patch.hip), not the per-pixel gather here
+  if (mode == 0 && co_real == 1 && head_ok(Cin, R, S, st, reflect, Wo) && !addend)
     return head_fwd_launch(in, wp, bias, out, N, Hi, Wi, Cin, Ho, Wo, R, S, pad, act, slope, s);
   {
     // few pixels, long K: split the K range over workgroups (skinny_split_k)

@@ -468,8 +468,8 @@ extern "C" int vst_tapconv_h_fwd(const float* x, const float* wp, const void* ws
     return tap64_launch(x, wsplit, (long)4 * R * R * Cx, bias, y, N, H, W, pad, pad_mode == VST_PAD_REFLECT, act,
                         slope, math, (hipStream_t)stream);
   // the R x 1 conv: rows padded by `pad`, the columns by 0 (their taps are summed below)
-  if (int e = vst_conv2d_fwd_hwp(x, wp, wsplit, nullptr, z, N, H, W, Cx, 4 * R, R, 1, 1, pad, 0, pad_mode,
-                                 VST_ACT_NONE, 0.f, math, stream))
+  if (int e = vst_conv2d_fwd_ex(x, wp, wsplit, nullptr, z, N, H, W, Cx, 4 * R, R, 1, 1, pad, 0, pad_mode,
+                                VST_ACT_NONE, 0.f, math, 4 * R, nullptr, nullptr, nullptr, 0, stream))
     return e;
   const long P = (long)N * Ho * Wo;
   const int refl = pad_mode == VST_PAD_REFLECT;

@@ -4,6 +4,7 @@ Every function launches on torch's current HIP stream, takes/returns torch tenso
 GPU, and raises on a non-zero status.  Activations are NHWC fp32 with a channel stride that is a
 multiple of 4 (``cpad``); images are NHWC4.  There is no CPU fallback: a CPU tensor is an error.
 """
+import ctypes
 import os
 import threading
 
@@ -199,10 +200,13 @@ def _probe_end(h):
         p.events.append(ev)
 
 
-# Split-K tails of x6 forward grids (vst_conv2d_fwd_ws); False keeps the small-tile tails.  (Module flags
-# like this one are route selectors the tests flip in-process to compare routes; they are not read from the
+# Split-K tails of x6 forward grids (the workspace of vst_conv2d_fwd_ex); False keeps the small-tile tails.  (Module
+# flags like this one are route selectors the tests flip in-process to compare routes; they are not read from the
 # environment.)
 FWD_SPLITK = True
+# conv2d_fwd_hw with the split-K plans of the square convs' workspace path (RAFT's SepConvGRU convs);
+# False: the one-launch plans
+FWD_HW_SPLITK = True
 
 # Planner answers the step asks for again and again are kept under keys that hold EVERY input of the answer: the
 # inputs given here (shape, arithmetic mode, the route switches read) and the calling thread's tile override — the C
@@ -219,72 +223,59 @@ def _memo(plan, *inputs):
     return r
 
 
-def _fwd_ws(N, H, W, Cx, cop, R, S, stride, pad, m, device):
-    """Workspace tensor of vst_conv2d_fwd_ws for this shape (None when the launch needs none)."""
-    nb = _memo(lib().vst_conv2d_fwd_ws_bytes, N, H, W, Cx, cop, R, S, stride, pad, m) if FWD_SPLITK else 0
-    if nb == 0:
-        return None, 0
-    return torch.empty((nb + 3) // 4, device=device), nb
+def _fwd_ex(x, wp, bias, cop, R, S, stride, pad_h, pad_w, pad_mode, act, slope, role, ws, sq=False, out=None,
+            co_real=None, stats=False):
+    """The one forward-conv launch (vst_conv2d_fwd_ex): y, or (y, part, nsplit) with stats.  ws: whether a workspace
+    is asked for (vst_conv2d_fwd_ex_ws_bytes) —
+      conv2d_fwd / conv2d_fwd_in:  FWD_SPLITK and S == R (sq: the answer memoized, the launch probed);
+      their co_real < cop path:    only for the head (cop == 4), no flag;
+      conv2d_fwd_hw:               FWD_HW_SPLITK."""
+    _dev_check(x, wp, bias)
+    N, H, W, Cx = x.shape
+    Ho = (H + 2 * pad_h - R) // stride + 1
+    Wo = (W + 2 * pad_w - S) // stride + 1
+    y = out if out is not None else torch.empty((N, Ho, Wo, cop), device=x.device)
+    m = _math(role)
+    co = cop if co_real is None else int(co_real)
+    nb = 0
+    if ws:
+        q = (N, H, W, Cx, cop, R, S, stride, pad_h, pad_w, PAD[pad_mode], m, co)
+        nb = _memo(lib().vst_conv2d_fwd_ex_ws_bytes, *q) if sq else int(lib().vst_conv2d_fwd_ex_ws_bytes(*q))
+    wsb = torch.empty((nb + 3) // 4, device=x.device) if nb else None
+    part = nsplit = None
+    if stats:
+        part = torch.empty((N * max(1, Ho * Wo // 32) * cop * 2,), device=x.device, dtype=torch.float64)
+        nsplit = ctypes.c_int(0)
+    h = _probe_begin("fwd", (N, H, W, Cx, cop, R, stride, pad_h, pad_mode)) if _probes and sq else None
+    _call("vst_conv2d_fwd_ex", _p(x), _p(wp), _p(getattr(wp, "vst_split", None)), _p(bias), _p(y), N, H, W, Cx, cop,
+          R, S, stride, pad_h, pad_w, PAD[pad_mode], ACT[act], float(slope), m, co, _p(part),
+          ctypes.addressof(nsplit) if stats else None, _p(wsb), nb, _stream())
+    _probe_end(h)
+    return (y, part, nsplit.value) if stats else y
 
 
 def conv2d_fwd(x, wp, bias, cop, R, S, stride, pad, pad_mode="zero", act="none", slope=0.0,
                out=None, role="fwd", co_real=None):
-    """co_real: the real output channels when cop pads them (vst_conv2d_fwd_co)."""
-    _dev_check(x, wp, bias)
+    """co_real: the real output channels when cop pads them (the PatchGAN head: 1 of 4)."""
     if co_real is not None and co_real < cop:
-        N, H, W, Cx = x.shape
-        Ho = (H + 2 * pad - R) // stride + 1
-        Wo = (W + 2 * pad - S) // stride + 1
-        y = out if out is not None else torch.empty((N, Ho, Wo, cop), device=x.device)
-        nb = int(lib().vst_conv2d_fwd_co_ws_bytes(N, H, W, Cx, cop, R, S, stride, pad, PAD[pad_mode], int(co_real)))
-        ws = torch.empty((nb + 3) // 4, device=x.device) if nb else None
-        _call("vst_conv2d_fwd_co_ws", _p(x), _p(wp), _p(getattr(wp, "vst_split", None)), _p(bias), _p(y), N, H, W,
-              Cx, cop, R, S, stride, pad, PAD[pad_mode], ACT[act], float(slope), _math(role), int(co_real), _p(ws), nb,
-              _stream())
-        return y
-    N, H, W, Cx = x.shape
-    Ho = (H + 2 * pad - R) // stride + 1
-    Wo = (W + 2 * pad - S) // stride + 1
-    y = out if out is not None else torch.empty((N, Ho, Wo, cop), device=x.device)
-    m = _math(role)
-    ws, nb = _fwd_ws(N, H, W, Cx, cop, R, S, stride, pad, m, x.device) if S == R else (None, 0)
-    h = _probe_begin("fwd", (N, H, W, Cx, cop, R, stride, pad, pad_mode)) if _probes else None
-    if ws is not None:
-        _call("vst_conv2d_fwd_ws", _p(x), _p(wp), _p(getattr(wp, "vst_split", None)), _p(bias), _p(y), N, H, W, Cx,
-              cop, R, S, stride, pad, PAD[pad_mode], ACT[act], float(slope), m, None, None, _p(ws), nb, _stream())
-    else:
-        _call("vst_conv2d_fwd", _p(x), _p(wp), _p(getattr(wp, "vst_split", None)), _p(bias), _p(y), N, H,
-              W, Cx, cop, R, S, stride, pad,
-              PAD[pad_mode], ACT[act], float(slope), m, _stream())
-    _probe_end(h)
-    return y
+        return _fwd_ex(x, wp, bias, cop, R, S, stride, pad, pad, pad_mode, act, slope, role, cop == 4, out=out,
+                       co_real=co_real)
+    return _fwd_ex(x, wp, bias, cop, R, S, stride, pad, pad, pad_mode, act, slope, role, FWD_SPLITK and S == R,
+                   sq=True, out=out)
 
 
 def conv2d_fwd_in(x, wp, bias, cop, R, S, stride, pad, pad_mode="zero", role="fwd"):
     """A conv that feeds an InstanceNorm: (y, stats).  The split-bf16 kernels emit the statistics
-    partials from their epilogue (vst_conv2d_fwd_in) and one small fold finalizes them; other paths
-    (fp32 policy, 4-channel inputs, image sizes not a multiple of 32 pixels) fall back to
+    partials from their epilogue (part / nsplit of vst_conv2d_fwd_ex) and one small fold finalizes them; other
+    paths (fp32 policy, 4-channel inputs, image sizes not a multiple of 32 pixels) fall back to
     instnorm_stats(y).  Same stats layout as instnorm_stats."""
-    import ctypes
-    _dev_check(x, wp, bias)
-    N, H, W, Cx = x.shape
-    Ho = (H + 2 * pad - R) // stride + 1
-    Wo = (W + 2 * pad - S) // stride + 1
-    y = torch.empty((N, Ho, Wo, cop), device=x.device)
-    hw = Ho * Wo
-    part = torch.empty((N * max(1, hw // 32) * cop * 2,), device=x.device, dtype=torch.float64)
-    nsplit = ctypes.c_int(0)
-    m = _math(role)
-    ws, nb = _fwd_ws(N, H, W, Cx, cop, R, S, stride, pad, m, x.device) if S == R else (None, 0)
-    h = _probe_begin("fwd", (N, H, W, Cx, cop, R, stride, pad, pad_mode)) if _probes else None
-    _call("vst_conv2d_fwd_ws", _p(x), _p(wp), _p(getattr(wp, "vst_split", None)), _p(bias), _p(y), N, H, W, Cx,
-          cop, R, S, stride, pad, PAD[pad_mode], ACT["none"], 0.0, m, _p(part),
-          ctypes.addressof(nsplit), _p(ws), nb, _stream())
-    _probe_end(h)
-    if nsplit.value == 0:
+    y, part, nsplit = _fwd_ex(x, wp, bias, cop, R, S, stride, pad, pad, pad_mode, "none", 0.0, role,
+                              FWD_SPLITK and S == R, sq=True, stats=True)
+    if nsplit == 0:
         return y, instnorm_stats(y)
+    N, Ho, Wo, _ = y.shape
     stats = torch.empty((N, cop, 2), device=x.device)
-    _call("vst_instnorm_finalize", _p(part), _p(stats), N, hw, cop, nsplit.value, IN_EPS, _stream())
+    _call("vst_instnorm_finalize", _p(part), _p(stats), N, Ho * Wo, cop, nsplit, IN_EPS, _stream())
     return y, stats
 
 
@@ -487,7 +478,7 @@ def _wgrad_plan(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride, m):
 
 
 def conv_plan_fwd_tail(N, H, W, Cx, Cop, R, S, stride, pad, math):
-    """Host-only: split-K count of the x6 tail launch vst_conv2d_fwd_ws runs for this shape (0: none)."""
+    """Host-only: split-K count of the x6 tail launch vst_conv2d_fwd_ex runs for this shape (0: none)."""
     import ctypes
     m = _math(math)
     ks = ctypes.c_int(0)
@@ -1492,28 +1483,9 @@ def u8_image_to_nhwc4(x):
 
 
 # ----------------------------------------------------------------------------------- RAFT
-# conv2d_fwd_hw with the split-K plans of the square convs' workspace path (RAFT's SepConvGRU convs);
-# False: the one-launch plans
-FWD_HW_SPLITK = True
-
-
 def conv2d_fwd_hw(x, wp, bias, cop, R, S, stride, pad_h, pad_w, act="none", role="fwd"):
-    """Forward conv with separate row / column zero padding (vst_conv2d_fwd_hw)."""
-    _dev_check(x, wp, bias)
-    N, H, W, Cx = x.shape
-    Ho = (H + 2 * pad_h - R) // stride + 1
-    Wo = (W + 2 * pad_w - S) // stride + 1
-    y = torch.empty((N, Ho, Wo, cop), device=x.device)
-    m = _math(role)
-    nb = int(lib().vst_conv2d_fwd_hw_ws_bytes(N, H, W, Cx, cop, R, S, stride, pad_h, pad_w, m)) if FWD_HW_SPLITK else 0
-    if nb:  # the split-K plans for small grids (vst_conv2d_fwd_hw_ws)
-        ws = torch.empty((nb + 3) // 4, device=x.device)
-        _call("vst_conv2d_fwd_hw_ws", _p(x), _p(wp), _p(getattr(wp, "vst_split", None)), _p(bias), _p(y), N, H, W,
-              Cx, cop, R, S, stride, pad_h, pad_w, ACT[act], 0.0, m, _p(ws), nb, _stream())
-        return y
-    _call("vst_conv2d_fwd_hw", _p(x), _p(wp), _p(getattr(wp, "vst_split", None)), _p(bias), _p(y), N, H, W, Cx,
-          cop, R, S, stride, pad_h, pad_w, ACT[act], 0.0, m, _stream())
-    return y
+    """Forward conv with separate row / column zero padding (RAFT's SepConvGRU (1,5) / (5,1) convs)."""
+    return _fwd_ex(x, wp, bias, cop, R, S, stride, pad_h, pad_w, "zero", act, 0.0, role, FWD_HW_SPLITK)
 
 
 def raft_prep(img, pads, nhwc=False, out=None):

@@ -132,18 +132,35 @@ enum { VST_MATH_F32 = 0, VST_MATH_BF16X3 = 1, VST_MATH_BF16X6 = 2 };
 int vst_conv2d_fwd(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
                    int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
                    int pad_mode, int act, float slope, int math, void* stream);
-/* Workspace of vst_conv2d_fwd_ws for this shape and arithmetic (0: the launch needs none).  Under
- * bf16x6 a grid that is not a whole number of 256x128-tile rounds runs its whole rounds as one
- * launch and the remaining pixel rows as a split-K launch (ks K ranges of the same 256x128 tiles)
- * whose partial tiles go to the workspace and are summed in split order by a reduction that applies
- * bias / act / the IN partials — instead of a launch of smaller tiles that leaves CUs idle. */
-size_t vst_conv2d_fwd_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
-                               int math);
-/* vst_conv2d_fwd (part == NULL) / vst_conv2d_fwd_in (part, nsplit) with a caller workspace ws of
- * ws_bytes >= vst_conv2d_fwd_ws_bytes (ws may be NULL when that is 0). */
-int vst_conv2d_fwd_ws(const float* x, const float* wp, const void* wsplit, const float* bias, float* y, int N,
-                      int H, int W, int Cx, int Cop, int R, int S, int stride, int pad, int pad_mode, int act,
-                      float slope, int math, double* part, int* nsplit, float* ws, size_t ws_bytes, void* stream);
+/* The full form of the forward conv: vst_conv2d_fwd with separate row / column padding (pad_h, pad_w:
+ * SepConvGRU's (1,5) / (5,1) kernels, update.py:36-43; Ho = (H + 2*pad_h - R)/stride + 1, Wo likewise with pad_w
+ * and S) and, each optional:
+ *   co_real     in [1, Cop]: the weight's output channels co_real..Cop-1 are padding (zero weight rows, zero
+ *               bias).  Read by the 4-output-channel path only (Cop == 4), which then computes only the real
+ *               ones (PatchGAN head: co_real = 1); the padded channels come out as act(0).  Cop: none is.
+ *   part,       both or neither (one alone: VST_EINVAL).  The InstanceNorm statistics partials of y from the GEMM
+ *   nsplit      epilogue (the conv that feeds an InstanceNorm): when the split-bf16 kernels run the conv and
+ *               Ho*Wo % 32 == 0, part (fp64, N * (Ho*Wo/32) * Cop * 2) receives {sum y, sum y^2} per (image,
+ *               32-pixel group, channel) and *nsplit = Ho*Wo/32; otherwise *nsplit = 0 (set on entry, on every
+ *               path) and the caller runs vst_instnorm_stats.  Replaces the statistics pass's full read of y
+ *               (networks.py InstanceNorm after each conv).
+ *   ws,         a caller workspace of ws_bytes >= vst_conv2d_fwd_ex_ws_bytes (NULL, or smaller: the conv runs
+ *   ws_bytes    without it).  Cop != 4: under bf16x6 a grid that is not a whole number of 256x128-tile rounds
+ *               runs its whole rounds as one launch and the remaining pixel rows as a split-K launch (ks K
+ *               ranges of the same 256x128 tiles) whose partial tiles go to the workspace and are summed in
+ *               split order by a reduction that applies bias / act / the IN partials — instead of a launch of
+ *               smaller tiles that leaves CUs idle; grids smaller than the CUs run as one such split-K launch
+ *               (PatchGAN layers, RAFT's SepConvGRU convs at 1/8 resolution).  pad_mode and co_real are not
+ *               read by that query.  Cop == 4 with co_real = 1 and pad_h == pad_w: the PatchGAN head
+ *               (networks.py:578; stride 1, zero padding, R, S <= 4, Cx a power of two in 32..1024) runs as a
+ *               per-input-row tap GEMM that reads x once (z[n][h][w][tap] in ws) plus a fixed-order tap sum
+ *               (patch.hip).  The two workspaces never coexist; 0: the launch takes none. */
+size_t vst_conv2d_fwd_ex_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h,
+                                  int pad_w, int pad_mode, int math, int co_real);
+int vst_conv2d_fwd_ex(const float* x, const float* wp, const void* wsplit, const float* bias, float* y, int N, int H,
+                      int W, int Cx, int Cop, int R, int S, int stride, int pad_h, int pad_w, int pad_mode, int act,
+                      float slope, int math, int co_real, double* part, int* nsplit, float* ws, size_t ws_bytes,
+                      void* stream);
 /* The data gradient of ReflectionPad2d(pad) + Conv2d(C -> 4, R x R) (the generator's last layer,
  * networks.py:365-366) without the padded frame: dx = vst_conv2d_fwd(dy, the VST_PACK_IKF pack, zero
  * padding pad) — the interior of the full correlation — then this pass adds, in a fixed order, the
@@ -152,34 +169,11 @@ int vst_conv2d_fwd_ws(const float* x, const float* wp, const void* wsplit, const
  * C % 16 == 0.  Replaces the conv over the (H+2pad) x (W+2pad) frame + vst_reflect_fold. */
 int vst_c4_dgrad_frame(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int R, int pad,
                        void* stream);
-/* Host-only: the split-K count (0 = none) vst_conv2d_fwd_ws uses for this shape and arithmetic: of
+/* Host-only: the split-K count (0 = none) vst_conv2d_fwd_ex uses for this shape and arithmetic: of
  * the tail launch, or — for grids of at most 128 256x128 tiles (PatchGAN layers, half batches) — of
  * the whole conv, run as one split-K launch + the reduction. */
 int vst_conv_plan_fwd_tail(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad, int math,
                            int* ksplit);
-/* vst_conv2d_fwd for a weight whose output channels co_real..Cop-1 are padding (zero weight rows,
- * zero bias): the 4-output-channel path (Cop == 4) then computes only the real ones (PatchGAN head:
- * co_real = 1); the padded channels come out as act(0), as from vst_conv2d_fwd. */
-int vst_conv2d_fwd_co(const float* x, const float* wp, const void* wsplit, const float* bias, float* y, int N, int H,
-                      int W, int Cx, int Cop, int R, int S, int stride, int pad, int pad_mode, int act, float slope,
-                      int math, int co_real, void* stream);
-/* vst_conv2d_fwd_co with a caller workspace of vst_conv2d_fwd_co_ws_bytes bytes (0: the shape takes no
- * workspace route, ws may be NULL): with co_real = 1 the PatchGAN head (networks.py:578; stride 1, zero
- * padding, R, S <= 4, Cx a power of two in 32..1024) runs as a per-input-row tap GEMM that reads x once
- * (z[n][h][w][tap] in ws) plus a fixed-order tap sum (patch.hip). */
-size_t vst_conv2d_fwd_co_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad,
-                                  int pad_mode, int co_real);
-int vst_conv2d_fwd_co_ws(const float* x, const float* wp, const void* wsplit, const float* bias, float* y, int N,
-                         int H, int W, int Cx, int Cop, int R, int S, int stride, int pad, int pad_mode, int act,
-                         float slope, int math, int co_real, float* ws, size_t ws_bytes, void* stream);
-/* vst_conv2d_fwd plus the InstanceNorm statistics partials of its output, from the GEMM epilogue
- * (the conv that feeds an InstanceNorm): when the split-bf16 kernels run the conv and Ho*Wo % 32 == 0,
- * part (fp64, N * (Ho*Wo/32) * Cop * 2) receives {sum y, sum y^2} per (image, 32-pixel group,
- * channel) and *nsplit = Ho*Wo/32; otherwise *nsplit = 0 and the caller runs vst_instnorm_stats.
- * Replaces the statistics pass's full read of y (networks.py InstanceNorm after each conv). */
-int vst_conv2d_fwd_in(const float* x, const float* wp, const void* wsplit, const float* bias, float* y, int N,
-                      int H, int W, int Cx, int Cop, int R, int S, int stride, int pad, int pad_mode, int act,
-                      float slope, int math, double* part, int* nsplit, void* stream);
 /* Transposed convolution / conv data-gradient (gather form, split by output parity class):
  *   out[n][h][w][cx] = sum_{r,s,cy : h = ho*stride - pad + r, w = wo*stride - pad + s}
  *                        in[n][ho][wo][cy] * w[cy][cx][r][s]        (+ bias[cx], act)
@@ -318,7 +312,7 @@ int vst_conv_plan_wgrad_chunk(int N, int H, int W, int Cx, int Ho, int Wo, int C
 /* Host-only route queries (no launch, no device needed), each the condition the launch itself tests:
  * vst_conv_plan_tfwd: *plan = VST_PLAN_SKINNY (Cx == 4, VALU) or VST_PLAN_RK ([row][k] kernel) of vst_conv2d_tfwd;
  * vst_tap64_ok: does vst_tapconv_h_fwd run the direct 64-channel 7 x 7 kernel (conv_tap64.hip) for this width;
- * vst_head_ok: do the one-real-channel head kernels (patch.hip) take vst_conv2d_fwd_co / _tfwd_co / the weight
+ * vst_head_ok: do the one-real-channel head kernels (patch.hip) take vst_conv2d_fwd_ex (co_real = 1) / _tfwd_co / the weight
  *   gradient with Co = 1 (Wo: the output width; for _tfwd_co the width of dy);
  * vst_img_wgrad_ok: does vst_conv2d_wgrad take the image-input kernel (patch.hip);
  * vst_skinny_split_ok: does a forward with 4 output channels run as K-range splits (skinny_split_k). */
@@ -344,7 +338,7 @@ size_t vst_instnorm_ws_bytes(int N, int HW, int C);
 int vst_instnorm_stats(const float* x, float* stats, float* ws, int N, int HW, int C, float eps,
                        void* stream);
 /* stats[n][c] = {mean, 1/sqrt(var + eps)} from fp64 partials part[n][z][c][2] = {sum, sum of squares}
- * over z < nsplit groups (vst_conv2d_fwd_in's epilogue partials); fixed-order fold. */
+ * over z < nsplit groups (vst_conv2d_fwd_ex's epilogue partials); fixed-order fold. */
 int vst_instnorm_finalize(const double* part, float* stats, int N, int HW, int C, int nsplit, float eps,
                           void* stream);
 /* y = act((x - mean) * rstd) (+ residual).  residual may be NULL. */
@@ -747,7 +741,7 @@ int vst_interleave_phases(const float* p00, const float* p01, const float* p10, 
 int vst_interleave_phases_full(const float* p00, const float* p01, const float* p10, const float* p11, float* y,
                                int N, int H, int W, int C, void* stream);
 /* One phase (a, b) in {0,1}^2 of a stride-2 ConvTranspose2d(k3, p1, op1) stored straight into the
- * interleaved output y [N][2H][2W][Cop]: the phase conv vst_conv2d_fwd_hw(x, phase pack, R = 1 + a,
+ * interleaved output y [N][2H][2W][Cop]: the phase conv vst_conv2d_fwd_ex(x, phase pack, R = 1 + a,
  * S = 1 + b, pad a / b) whose pixel (ph, pw) is y's (2(ph-a)+a, 2(pw-b)+b).  Four calls write every
  * pixel of y once, replacing four phase images + vst_interleave_phases.  wsplit = the phase pack's bf16
  * planes; Cx % 8 == 0; split-bf16 math only (VST_EUNSUPPORTED for VST_MATH_F32). */
@@ -768,22 +762,6 @@ int vst_conv4s2_dgrad(const float* dy, const void* ws00, const void* ws01, const
                       float* dx, int N, int Hd, int Wd, int Cy, int Cop, int math, void* stream);
 
 /* ---- RAFT inference (SURVEY §8 A19 + §8f rank 3) ------------------------------------------ */
-/* Forward conv with separate row / column zero padding (SepConvGRU's (1,5) / (5,1) kernels with
- * padding (0,2) / (2,0), update.py:36-43); otherwise identical to vst_conv2d_fwd. */
-int vst_conv2d_fwd_hw(const float* x, const float* wp, const void* wsplit, const float* bias, float* y,
-                      int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h, int pad_w,
-                      int act, float slope, int math, void* stream);
-/* vst_conv2d_fwd_hw with a caller-owned workspace: the split-K plans of vst_conv2d_fwd_ws for grids smaller than
- * the CUs (ws_bytes >= vst_conv2d_fwd_hw_ws_bytes; ws may be NULL when that is 0). */
-size_t vst_conv2d_fwd_hw_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h,
-                                  int pad_w, int math);
-int vst_conv2d_fwd_hw_ws(const float* x, const float* wp, const void* wsplit, const float* bias, float* y, int N,
-                         int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h, int pad_w, int act,
-                         float slope, int math, float* ws, size_t ws_bytes, void* stream);
-/* vst_conv2d_fwd_hw with a padding mode (VST_PAD_ZERO / VST_PAD_REFLECT). */
-int vst_conv2d_fwd_hwp(const float* x, const float* wp, const void* wsplit, const float* bias, float* y, int N, int H,
-                       int W, int Cx, int Cop, int R, int S, int stride, int pad_h, int pad_w, int pad_mode, int act,
-                       float slope, int math, void* stream);
 /* InputPadder.pad (utils/raft/raft/utils/utils.py:7-20, replicate) + raft.py:89-90 2*(x/255)-1:
  * NCHW [B][3][H][W] -> NHWC4 [B][H+pt+pb][W+pl+pr][4]. */
 int vst_raft_prep(const float* img, float* out, int B, int H, int W, int pad_l, int pad_r, int pad_t,
@@ -842,9 +820,9 @@ int vst_u8_image_to_nhwc4(const unsigned char* x, float* y, long npix, void* str
  * shape-argument API above spells differently.  These wrappers give a binder written from §8b the
  * names it expects; each forwards to the kernels above (no extra launch except where stated).
  *   §8b name                         forwards to
- *   vst_conv2d_fwd/dgrad/wgrad(desc) vst_conv2d_fwd_ws / vst_conv2d_tfwd / vst_conv2d_wgrad (the
+ *   vst_conv2d_fwd/dgrad/wgrad(desc) vst_conv2d_fwd_ex / vst_conv2d_tfwd / vst_conv2d_wgrad (the
  *                                    `_desc` suffix: the shape-argument names are taken above)
- *   vst_workspace_size               vst_conv2d_fwd_ws_bytes / vst_conv2d_wgrad_ws_bytes
+ *   vst_workspace_size               vst_conv2d_fwd_ex_ws_bytes / vst_conv2d_wgrad_ws_bytes
  *   vst_warp_bilinear_fwd/bwd_input  vst_warp_fwd / vst_warp_masked_fwd (validity mask flag)
  *   vst_masked_sqdiff_mean_fwd/bwd   vst_loss_temporal(_bwd)   (fused warp + masked squared diff)
  *   vst_l1_mean_fwd/bwd              vst_loss_l1(_bwd)
@@ -879,7 +857,7 @@ int vst_conv_desc_out_hw(const vst_conv_desc* d, int* Ho, int* Wo);
 size_t vst_workspace_size(const vst_conv_desc* d, int op);
 /* Forward: y = act(conv(x) + bias).  wp: VST_PACK_OK pack (+ wsplit planes) of a Conv2d weight, or
  * the VST_PACK_IK pack of a ConvTranspose2d weight.  in_part / in_nsplit: optional InstanceNorm
- * partials (vst_conv2d_fwd_in; direct convs). */
+ * partials (part / nsplit of vst_conv2d_fwd_ex; direct convs). */
 int vst_conv2d_fwd_desc(const vst_conv_desc* d, const float* x, const float* wp, const void* wsplit,
                         const float* bias, float* y, double* in_part, int* in_nsplit, float* ws, size_t ws_bytes,
                         void* stream);

@@ -587,7 +587,7 @@ def run_wgrad(ops, c, x, dy, prefill=None, planes=False):
 
 
 def run_fwd_head(ops, c, x, w, bias=None, act="none", slope=0.0):
-    """One real output channel padded to 4 (the PatchGAN head, vst_conv2d_fwd_co_ws)."""
+    """One real output channel padded to 4 (the PatchGAN head: vst_conv2d_fwd_ex with co_real = 1 and its workspace)."""
     wp = ops.weight_pack(_dev(w), ops.PACK_FWD)
     y = ops.conv2d_fwd(ops.nchw_to_nhwc(_dev(x)), wp, _bias(ops, bias, 1), 4, c.R, c.S, c.stride, c.ph, c.mode, act, slope,
                        co_real=1)
@@ -919,8 +919,8 @@ def _fwd_tail(ops, c, m):  # whole rounds of 256x128 tiles, then the last partia
 
 
 def _head_fwd(ops, c, m):
-    return c.Co == 1 and int(ops.lib().vst_conv2d_fwd_co_ws_bytes(c.N, c.H, c.W, cpad(c.Ci), 4, c.R, c.S, c.stride, c.ph,
-                                                                  ops.PAD[c.mode], 1)) > 0
+    return c.Co == 1 and int(ops.lib().vst_conv2d_fwd_ex_ws_bytes(c.N, c.H, c.W, cpad(c.Ci), 4, c.R, c.S, c.stride, c.ph,
+                                                                  c.ph, ops.PAD[c.mode], ops._math(m), 1)) > 0
 
 
 def _head_ok(ops, c, m):  # the head kernels' own condition (vst_head_ok) on the width of dy

@@ -132,7 +132,7 @@ def _compiles(tmp_path, name, source):
 
 def test_compiler_agrees_with_the_parsed_signatures_and_struct(tmp_path):
     from gbvst import _lib
-    assert len(_lib.SIGNATURES) >= 179
+    assert len(_lib.SIGNATURES) >= 177  # the header declares 177 entry points
     assert [n for n, _ in _lib.VstConvDesc._fields_][-2:] == ["slope", "math"]
     ok, out = _compiles(tmp_path, "abi_ok.cpp", _checker_source(_lib.SIGNATURES, _lib.VstConvDesc))
     assert ok, out

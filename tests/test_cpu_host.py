@@ -384,3 +384,55 @@ def test_route_overrides_reject_malformed_arms(monkeypatch):
     monkeypatch.setenv("VST_ROUTES", "ops.NO_SUCH_FLAG=0")
     with pytest.raises(ValueError):
         _lib.apply_route_overrides("gbvst.ops", dict(g))
+
+
+_FWD_REMOVED = ("vst_conv2d_fwd_co", "vst_conv2d_fwd_co_ws", "vst_conv2d_fwd_co_ws_bytes", "vst_conv2d_fwd_in",
+                "vst_conv2d_fwd_ws", "vst_conv2d_fwd_ws_bytes", "vst_conv2d_fwd_hw", "vst_conv2d_fwd_hwp",
+                "vst_conv2d_fwd_hw_ws", "vst_conv2d_fwd_hw_ws_bytes")
+
+
+def test_the_forward_conv_has_one_full_entry_point():
+    import gbvst
+    sig = gbvst._lib.SIGNATURES
+    assert not [n for n in _FWD_REMOVED if n in sig]
+    assert {"vst_conv2d_fwd", "vst_conv2d_fwd_desc", "vst_conv2d_fwd_ex", "vst_conv2d_fwd_ex_ws_bytes"} <= set(sig)
+
+
+def _fwd_ex(lib, co_real, part, nsplit, Cop=8):
+    # device pointers that are never dereferenced: the argument checks come before any device call
+    x = wp = y = ctypes.c_void_p(256)
+    return lib.vst_conv2d_fwd_ex(x, wp, None, None, y, 1, 8, 8, 8, Cop, 3, 3, 1, 1, 1, 0, 0, 0.0, 0, co_real, part,
+                                 nsplit, None, 0, None)
+
+
+@pytest.mark.parametrize("case", ["co_real_0", "co_real_over", "part_alone", "nsplit_alone"])
+def test_fwd_ex_refuses_bad_optional_arguments_on_the_host(case):
+    import gbvst
+    lib = gbvst._lib.load()
+    einval = gbvst._lib.CONSTANTS["VST_EINVAL"]
+    part, ns = (ctypes.c_double * 4)(), ctypes.c_int(7)
+    if case == "co_real_0":
+        rc = _fwd_ex(lib, 0, None, None)
+    elif case == "co_real_over":
+        rc = _fwd_ex(lib, 9, None, None)
+    elif case == "part_alone":
+        rc = _fwd_ex(lib, 8, ctypes.addressof(part), None)
+    else:
+        rc = _fwd_ex(lib, 8, None, ctypes.addressof(ns))
+        assert ns.value == 0  # *nsplit is cleared on entry, on the error paths too
+    assert rc == einval, lib.vst_last_error()
+
+
+def test_fwd_ex_ws_bytes_is_zero_for_a_non_positive_shape():
+    import gbvst
+    lib = gbvst._lib.load()
+    x6 = gbvst._lib.MATH_MODES["bf16x6"]
+    good = dict(N=1, H=64, W=64, Cx=256, Cop=256, R=3, S=3, stride=1, pad_h=1, pad_w=1, pad_mode=0, math=x6, co_real=256)
+    assert lib.vst_conv2d_fwd_ex_ws_bytes(*good.values()) > 0      # a split-K plan: the zeros below are the shape's doing
+    head = dict(good, H=31, W=31, Cx=512, Cop=4, R=4, S=4, co_real=1)
+    assert lib.vst_conv2d_fwd_ex_ws_bytes(*head.values()) > 0      # the PatchGAN head's tap GEMM
+    for base in (good, head):
+        for k in ("N", "H", "W", "R", "S", "stride"):
+            for v in (0, -1):
+                assert lib.vst_conv2d_fwd_ex_ws_bytes(*dict(base, **{k: v}).values()) == 0, (k, v)
+        assert lib.vst_conv2d_fwd_ex_ws_bytes(*dict(base, H=1, W=1, pad_h=0, pad_w=0).values()) == 0  # empty output

@@ -605,7 +605,7 @@ def test_production_resnet_conv(ops, conv_math, forced):
     (2, 34, 34, 64, 128, 4, 1, 1, "zero"),       # 33x33 output (not a multiple of 32 px): fallback
 ])
 def test_conv_fwd_in_stats(ops, case, conv_math):
-    """vst_conv2d_fwd_in: the conv output equals vst_conv2d_fwd's, and the InstanceNorm statistics
+    """vst_conv2d_fwd_ex with part / nsplit (ops.conv2d_fwd_in): the conv output equals vst_conv2d_fwd's, and the InstanceNorm statistics
     folded from its epilogue partials equal vst_instnorm_stats of that output (fp64 partial sums in
     another order: mean and rstd to 1e-6 relative)."""
     N, H, W, Cx, Cop, R, st, pad, mode = case
@@ -790,7 +790,7 @@ def test_instnorm_fwd_cp_and_wgrad_exact(ops, st, mode, res):
 
 @pytest.mark.parametrize("N,pad", [(8, 2), (12, 1), (12, 2)], ids=["n8_dgrad_frame", "n12_fwd", "n12_dgrad_frame"])
 def test_splitk_tail_vs_small_tiles_and_torch(ops, N, pad):
-    """The x6 split-K wave-quantisation tail (vst_conv2d_fwd_ws: whole rounds of 256x128 tiles, then
+    """The x6 split-K wave-quantisation tail (the workspace of vst_conv2d_fwd_ex: whole rounds of 256x128 tiles, then
     the remaining rows as ks K-range splits of the same tiles + an in-order reduction with bias and
     the IN partials) against the small-tile tail (no workspace) and torch fp32 on the CPU.  Shapes:
     the ResnetBlock conv as the batched train step runs it (N=12 forward; the 66x66-frame data
@@ -935,7 +935,7 @@ def test_conv_fwd_skinny_split(ops, shape):
 @pytest.mark.parametrize("shape", [(2, 512, 31, 31, 1, "zero", "none"), (1, 64, 9, 7, 2, "zero", "lrelu"),
                                    (1, 36, 12, 10, 1, "reflect", "tanh")])
 def test_conv_fwd_one_real_channel(ops, shape):
-    """vst_conv2d_fwd_co with co_real = 1 (the PatchGAN head: one real channel padded to 4): the
+    """vst_conv2d_fwd_ex with co_real = 1 (the PatchGAN head: one real channel padded to 4): the
     padded channels equal the 4-channel path's exactly, the real one agrees with it to fp32 rounding
     (the compiler contracts the one-channel sum into a different FMA chain) and matches torch."""
     N, Ci, H, W, st, mode, act = shape

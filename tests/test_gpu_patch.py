@@ -1,5 +1,5 @@
 """The PatchGAN head — Conv2d(8*ndf, 1, 4, stride 1, padding 1), networks.py:576-578 — on its row
-kernels (csrc/patch.hip): forward (vst_conv2d_fwd_co, co_real = 1), weight gradient (vst_conv2d_wgrad
+kernels (csrc/patch.hip): forward (vst_conv2d_fwd_ex, co_real = 1), weight gradient (vst_conv2d_wgrad
 with Co = 1) and data gradient (vst_conv2d_tfwd_co) against torch fp32 autograd on the same inputs.
 fp32 FMA chains on both sides, only the summation order differs: |err| <= 2e-5 * max|ref| + 1e-6.
 Shapes: the C2 head (N = 8 / 4 at 31x31x512), the C3 Sintel-size head (27 x 64 input: column

@@ -114,8 +114,9 @@ def layers(steps):
         if name in ("conv2d_fwd", "conv2d_fwd_in"):
             x, _, _, cop, R, S, st, pad = a[:8]
             N, H, W, Cx = x.shape
-            ws, _ = ops._fwd_ws(N, H, W, Cx, cop, R, S, st, pad, ops._math(k.get("role", "fwd")), x.device)
-            return "%s -> %d k%d s%d" % (shape(x), cop, R, st), "split-K" if ws is not None else "one pass"
+            nb = ops.FWD_SPLITK and S == R and ops.lib().vst_conv2d_fwd_ex_ws_bytes(
+                N, H, W, Cx, cop, R, S, st, pad, pad, ops.PAD["zero"], ops._math(k.get("role", "fwd")), cop)
+            return "%s -> %d k%d s%d" % (shape(x), cop, R, st), "split-K" if nb else "one pass"
         if name in ("conv4s2_dgrad", "convT4s2_fwd"):
             x, packs, cop = a[0], a[1], a[2] if name == "conv4s2_dgrad" else a[3]
             N, Hd, Wd, Cy = x.shape
