@@ -620,6 +620,10 @@ extern "C" int vst_conv2d_fwd_ex(const float* x, const float* wp, const void* ws
   if (nsplit) *nsplit = 0;
   VST_REQUIRE(co_real >= 1 && co_real <= Cop, "conv2d_fwd_ex: bad real channel count %d", co_real);
   VST_REQUIRE(!part == !nsplit, "conv2d_fwd_ex: part and nsplit go together");
+  if (ws && ws_bytes) {  // no workspace (NULL / 0 bytes) is a route of its own; one that is too small is an error
+    const size_t need = vst_conv2d_fwd_ex_ws_bytes(N, H, W, Cx, Cop, R, S, stride, pad_h, pad_w, pad_mode, math, co_real);
+    VST_REQUIRE(ws_bytes >= need, "conv2d_fwd_ex: workspace too small (%zu of %zu bytes)", ws_bytes, need);
+  }
   if (Cop == 4 && ws && x && wp && y) {
     const size_t need = head_tap_ws_bytes(N, H, W, Cx, R, S, stride, pad_h, pad_w, pad_mode, co_real);
     if (need && ws_bytes >= need) {
@@ -861,14 +865,14 @@ extern "C" int vst_conv2d_wgrad_pre(const float* x, const float* x_t, const floa
               "conv2d_wgrad: channel strides must be multiples of 4");
   VST_REQUIRE(Co <= Cyp && Ci <= Cx, "conv2d_wgrad: logical channels exceed strides");
   VST_REQUIRE(pad_mode == VST_PAD_ZERO || (pad < H && pad < W), "conv2d_wgrad: reflect pad >= size");
-  if (!x_t && !dy_planes && img_wgrad_ok(Cx, Cyp, R, S, stride, pad_mode == VST_PAD_REFLECT, Ci, Wo) &&
-      Co <= Cyp && ws_bytes >= img_wgrad_ws_floats(N, Ho, Wo) * sizeof(float))
+  // the query covers every route below (each arithmetic's plan, the head and the image-input kernels)
+  VST_REQUIRE(ws_bytes >= vst_conv2d_wgrad_ws_bytes(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride),
+              "conv2d_wgrad: workspace too small (%zu bytes)", ws_bytes);
+  if (!x_t && !dy_planes && img_wgrad_ok(Cx, Cyp, R, S, stride, pad_mode == VST_PAD_REFLECT, Ci, Wo))
     return img_wgrad_launch(x, dy, dw, nullptr, ws, N, H, W, Ho, Wo, Cyp, R, S, stride, pad, Co, Ci, so, si, accumulate,
                             (hipStream_t)stream);
   int Cxg;  // the GEMM's channel count (3 for image-input layers)
   const WgradPlan p = plan_wgrad_gemm(p0, N, H, W, Ho, Wo, Cx, Ci, Cyp, R, S, stride, math, &Cxg);
-  VST_REQUIRE(ws_bytes >= wgrad_ws_floats(p, Cyp) * sizeof(float),
-              "conv2d_wgrad: workspace too small (%zu bytes)", ws_bytes);
   hipStream_t s = (hipStream_t)stream;
   const int P = N * Ho * Wo;
   const int refl = pad_mode == VST_PAD_REFLECT;
@@ -902,8 +906,7 @@ extern "C" int vst_conv2d_wgrad_pre(const float* x, const float* x_t, const floa
       rk_wgrad_launch(xt, dyt, ws, N, H, W, Cx, Ho, Wo, Cyp, S, pad, stride, p.Mw, p.chunk, p.nsplit,
                       (int)p.tile, math, s);
     }
-  } else if (Cyp == 4 && Co == 1 && head_ok(Cx, R, S, stride, refl, Wo) &&
-             ws_bytes >= head_wgrad_ws_floats(N, H, Cx, R, S) * sizeof(float)) {
+  } else if (Cyp == 4 && Co == 1 && head_ok(Cx, R, S, stride, refl, Wo)) {
     // the PatchGAN head: the activation read once, partials reduced in a fixed order straight into dw
     return head_wgrad_launch(x, dy, dw, ws, N, H, W, Cx, Ci, Ho, Wo, R, S, pad, si, accumulate, s);
   } else if (Cyp == 4) {
@@ -1162,13 +1165,13 @@ extern "C" int vst_conv2d_wgrad_bias(const float* x, const float* dy, float* dw,
   VST_REQUIRE(x && dy && dw && db && ws && N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && R > 0 && S > 0 &&
                   stride > 0 && pad >= 0 && Co >= 1 && Co <= Cyp && Ci >= 1 && Ci <= Cx,
               "conv2d_wgrad_bias: bad args");
+  VST_REQUIRE(ws_bytes >= vst_conv2d_wgrad_ws_bytes(N, H, W, Cx, Ho, Wo, Cyp, R, S, stride),
+              "conv2d_wgrad_bias: workspace too small (%zu bytes)", ws_bytes);
   const int refl = pad_mode == VST_PAD_REFLECT;
   hipStream_t s = (hipStream_t)stream;
-  if (img_wgrad_ok(Cx, Cyp, R, S, stride, refl, Ci, Wo) &&
-      ws_bytes >= img_wgrad_ws_floats(N, Ho, Wo) * sizeof(float))
+  if (img_wgrad_ok(Cx, Cyp, R, S, stride, refl, Ci, Wo))
     return img_wgrad_launch(x, dy, dw, db, ws, N, H, W, Ho, Wo, Cyp, R, S, stride, pad, Co, Ci, so, si, accumulate, s);
-  if (Cyp == 4 && Co == 1 && head_ok(Cx, R, S, stride, refl, Wo) &&
-      ws_bytes >= head_wgrad_ws_floats(N, H, Cx, R, S) * sizeof(float))
+  if (Cyp == 4 && Co == 1 && head_ok(Cx, R, S, stride, refl, Wo))
     return head_wgrad_launch(x, dy, dw, ws, N, H, W, Cx, Ci, Ho, Wo, R, S, pad, si, accumulate, s, db);
   ::vst::set_error("conv2d_wgrad_bias: no fused route for this shape (use vst_conv2d_wgrad + vst_channel_sum)");
   return VST_EUNSUPPORTED;

@@ -144,17 +144,18 @@ int vst_conv2d_fwd(const float* x, const float* wp, const void* wsplit, const fl
  *               32-pixel group, channel) and *nsplit = Ho*Wo/32; otherwise *nsplit = 0 (set on entry, on every
  *               path) and the caller runs vst_instnorm_stats.  Replaces the statistics pass's full read of y
  *               (networks.py InstanceNorm after each conv).
- *   ws,         a caller workspace of ws_bytes >= vst_conv2d_fwd_ex_ws_bytes (NULL, or smaller: the conv runs
- *   ws_bytes    without it).  Cop != 4: under bf16x6 a grid that is not a whole number of 256x128-tile rounds
- *               runs its whole rounds as one launch and the remaining pixel rows as a split-K launch (ks K
- *               ranges of the same 256x128 tiles) whose partial tiles go to the workspace and are summed in
- *               split order by a reduction that applies bias / act / the IN partials — instead of a launch of
- *               smaller tiles that leaves CUs idle; grids smaller than the CUs run as one such split-K launch
- *               (PatchGAN layers, RAFT's SepConvGRU convs at 1/8 resolution).  pad_mode and co_real are not
- *               read by that query.  Cop == 4 with co_real = 1 and pad_h == pad_w: the PatchGAN head
- *               (networks.py:578; stride 1, zero padding, R, S <= 4, Cx a power of two in 32..1024) runs as a
- *               per-input-row tap GEMM that reads x once (z[n][h][w][tap] in ws) plus a fixed-order tap sum
- *               (patch.hip).  The two workspaces never coexist; 0: the launch takes none. */
+ *   ws,         a caller workspace of ws_bytes >= vst_conv2d_fwd_ex_ws_bytes (NULL or 0 bytes: the conv runs
+ *   ws_bytes    without it; 0 < ws_bytes < the query: VST_EINVAL, nothing is launched).  Cop != 4: under bf16x6
+ *               a grid that is not a whole number of 256x128-tile rounds runs its whole rounds as one launch and
+ *               the remaining pixel rows as a split-K launch (ks K ranges of the same 256x128 tiles) whose
+ *               partial tiles go to the workspace and are summed in split order by a reduction that applies
+ *               bias / act / the IN partials — instead of a launch of smaller tiles that leaves CUs idle; grids
+ *               smaller than the CUs run as one such split-K launch (PatchGAN layers, RAFT's SepConvGRU convs
+ *               at 1/8 resolution).  pad_mode and co_real are not read by that query.  Cop == 4 with
+ *               co_real = 1 and pad_h == pad_w: the PatchGAN head (networks.py:578; stride 1, zero padding,
+ *               R, S <= 4, Cx a power of two in 32..1024) runs as a per-input-row tap GEMM that reads x once
+ *               (z[n][h][w][tap] in ws) plus a fixed-order tap sum (patch.hip).  The two workspaces never
+ *               coexist; 0: the launch takes none. */
 size_t vst_conv2d_fwd_ex_ws_bytes(int N, int H, int W, int Cx, int Cop, int R, int S, int stride, int pad_h,
                                   int pad_w, int pad_mode, int math, int co_real);
 int vst_conv2d_fwd_ex(const float* x, const float* wp, const void* wsplit, const float* bias, float* y, int N, int H,
